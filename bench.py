@@ -23,7 +23,13 @@ Math modes (include/xsd.h: xsd_set_math), all with fp32 planes and fp32 MFMA acc
 torch.distributed.run; the parent never touches the GPU) and relays rank 0's JSON line; under an external torchrun it
 runs as a rank.  XSD_DIST_BACKEND=gloo rehearses the multi-rank path on a box with fewer GPUs than ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up, warm up, time the K steps (no per-launch
+events, no sampling thread), write the last step's outputs when --dump-outputs DIR is given, print the line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, `steps`, `warmup`, `config`.  --dump-outputs DIR writes what the timed path
+returned in its last timed step as DIR/<name>.npy (float32): a train step's `loss`, the parameters after its Adam update
+(`params`) and its flat gradient (`grads`); a forward's `output`.  An array that would take the files past 64 MB is replaced by a
+fixed, seeded sample of its flat elements (`<name>_sample`).  Inputs are seeded: the same arguments give the same inputs.
+--full adds everything else the line has carried (each part can still be switched off by its --no-* option):
   roofline     : the dominant kernel's algorithmic FLOP (or bytes) / its average HIP-event launch time inside the timed
                  region against the peak that binds the mode (MI355X_MICROARCH.md); `sustained_peak` / `frac_of_sustained`: the
                  same against what THIS device sustains on the conv's bare MFMA stream, measured in this process after the timed
@@ -35,7 +41,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   comm_ms_exposed / per_rank (N > 1): what the compute stream waited for the gradient exchange; every rank's own step time,
                  device clock, watts and sustained matrix rate -- a < N x curve separates device spread from communication,
   cpu_baseline : the same train step (B=1) through oracle/oracle.py's torch restatement on the host cores (1 warm-up step,
-                 then best of 3; every sample recorded).
+                 then best of 3; every sample recorded),
+  unprofiled   : with the roofline's per-launch events in the headline's timed region, the same K steps again without them,
+  extra        : the strict math mode over the same --steps/--warmup (N = 1).
 """
 import argparse
 import json
@@ -352,6 +360,35 @@ def psnr_delta_vs_reference(kind, math, dev):
                      "reference_from": "tests/golden/example_data.npz (written from the imported reference by tests/golden/make_golden.py)"}}
 
 
+DUMP_LIMIT_BYTES = 64_000_000     # --dump-outputs: all files together, headers included
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: `arrays` = {name: array-like} in order; written as DIR/<name>.npy in float32 (float64 stays float64).  While
+    the files would pass `limit` bytes, the largest array is replaced by a fixed sample of k of its n flat elements (k as many as
+    fit), DIR/<name>_sample.npy: one element from each of k consecutive blocks of about n / k, its offset in the block drawn from a
+    generator seeded with 0 -- the same positions for the same shapes, whichever build wrote it.  Returns {file name: shape written}."""
+    import numpy as np
+    data = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        data[name] = np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    header = 128            # an .npy header of these shapes
+    while sum(a.nbytes + header for a in data.values()) > limit:
+        name = max(data, key=lambda n: data[n].nbytes)
+        a = data.pop(name).reshape(-1)
+        room = limit - sum(b.nbytes + header for b in data.values()) - header
+        k = room // a.itemsize
+        if k < 1:
+            raise ValueError(f"--dump-outputs: no room left under {limit} bytes for {name}")
+        edges = np.arange(k + 1, dtype=np.int64) * a.size // k        # k blocks of n / k elements (k < n here)
+        data[name + "_sample"] = a[edges[:-1] + np.random.default_rng(0).integers(0, np.diff(edges))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in data.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in data.items()}
+
+
 def self_launch(args) -> int:
     """--gpus N > 1 outside torchrun: start the N ranks as children of torch.distributed.run and relay their output.
     This parent never initialises the GPU (no torch.cuda call, no HIP library loaded) and does not exec."""
@@ -400,6 +437,13 @@ def main():
     ap.add_argument("--filters", type=int, default=32,
                     help="num_filters of the generator (BASELINE: 32 = res/configs/models.toml).  Other widths are NOT the headline: "
                          "the line then carries no cpu_baseline, no PMC traffic and no whole-step figures (those are defined for 32)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (per-launch events in the timed region, then the same K steps unprofiled), "
+                         "power, sustained MFMA rate, PSNR deltas, the extra math leg, the CPU baseline and, with N > 1, the per-rank "
+                         "block, exposed exchange wait and replica check (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "train: loss, params after Adam, grads; forward: output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--extra-math", default="bf16x6", choices=sorted(MATHS) + ["none"],
@@ -514,7 +558,8 @@ def main():
             return model(x)
 
     def timed(nwarm, nsteps, profile, watch=None):
-        """-> (max-over-ranks seconds, this rank's own seconds, profile records, exposed communication ms per step on this rank)"""
+        """-> (max-over-ranks seconds, this rank's own seconds, profile records, exposed communication ms per step on this rank
+        (--full), what the last step returned)"""
         for i in range(nwarm):
             step()
             trace(f"warm-up step {i} enqueued")
@@ -523,14 +568,15 @@ def main():
         if dp:
             dist.barrier()
         torch.cuda.synchronize()
-        if train:
+        if train and args.full:
             trainer.comm_events_begin()       # event pair around the wait for the gradient exchange, read after the timed region
         if watch is not None:
             watch.start()
         trace("timed region starts")
         t0 = time.perf_counter()
+        last = None
         for _ in range(nsteps):
-            step()
+            last = step()
         torch.cuda.synchronize()
         mine = time.perf_counter() - t0       # this rank's own K steps (before the closing barrier): the per-rank figure
         trace("timed region done")
@@ -543,29 +589,40 @@ def main():
             tt = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        comm_ms = trainer.comm_events_end() / nsteps if train else None
+        comm_ms = trainer.comm_events_end() / nsteps if (train and args.full) else None
         prof = None
         if profile:
             prof = {k: eng.profile_read(k) for k in range(len(PROFILE_CLASSES))}
             eng.profile_enable(False)
-        return dt, mine, prof, comm_ms
+        return dt, mine, prof, comm_ms, last
 
-    # every rank watches ITS OWN device (by PCI address): the per-rank block below carries each device's clock and watts
-    my_pci = device_pci(dev.index if hasattr(dev, "index") and dev.index is not None else 0)
-    pwatch = PowerWatch(pci=[my_pci] if my_pci else None)
-    dt, my_dt, prof, comm_ms = timed(args.warmup, args.steps, not args.no_profile, pwatch)
-    power = pwatch.summary()
+    # --full: every rank watches ITS OWN device (by PCI address): the per-rank block below carries each device's clock and watts
+    my_pci = device_pci(dev.index if hasattr(dev, "index") and dev.index is not None else 0) if args.full else None
+    pwatch = PowerWatch(pci=[my_pci] if my_pci else None) if args.full else None
+    dt, my_dt, prof, comm_ms, last = timed(args.warmup, args.steps, args.full and not args.no_profile, pwatch)
+    power = pwatch.summary() if pwatch is not None else None
+
+    # --dump-outputs: what the last timed step returned, before anything else runs on this model
+    if args.dump_outputs and rank == 0:
+        if train:
+            outs = {"loss": torch.as_tensor(last).detach().float().cpu().numpy(), "params": trainer.flat.detach().cpu().numpy(),
+                    "grads": trainer.grads.detach().cpu().numpy()}
+        else:
+            outs = {"output": last.detach().cpu().numpy()}
+        written = write_outputs(args.dump_outputs, outs)
+        print(f"bench.py: wrote {written} to {args.dump_outputs}", file=sys.stderr)
+
     # The headline's timed region carries the per-launch HIP events the roofline block is computed from (two hipEventRecord per
     # MFMA-kernel launch: ~0.2 % of a batch-32 step, ~10 % of a batch-1 step).  The same K steps once more WITHOUT them, reported
     # beside the headline as `unprofiled` -- what a user's step costs
     dt_plain = None
-    if not args.no_profile:
-        dt_plain, _, _, _ = timed(0, args.steps, False)
+    if args.full and not args.no_profile:
+        dt_plain, _, _, _, _ = timed(0, args.steps, False)
 
     # the rate the matrix pipes of THIS device sustain on the conv's bare MFMA stream, measured now, in this process
     # (include/xsd.h: xsd_probe_mfma_stream): the roof the package power cap leaves of the nominal 2.5 PFLOP/s
     sustained = None
-    if args.math in MATH_PRODUCTS and not args.no_sustained:
+    if args.full and args.math in MATH_PRODUCTS and not args.no_sustained:
         fmt = "f16" if args.math == "f16x3" else "bf16"
         if dp and world > ndev:      # a rehearsal with ranks SHARING a device: one rank at a time, or per_rank.sustained_mfma_tflops is a contended figure that reads as device spread
             for r in range(world):
@@ -576,7 +633,7 @@ def main():
             sustained = eng.probe_mfma_stream(fmt, args.sustained_seconds)
 
     per_rank = None
-    if dp:      # what a < N x curve is made of: every rank's own step time, device clock and watts, exposed exchange wait
+    if dp and args.full:      # what a < N x curve is made of: every rank's own step time, device clock and watts, exposed exchange wait
         mine_rec = {"ms_per_step": round(1e3 * my_dt / args.steps, 3), "sclk_mhz": power["sclk_mhz"] if power else None,
                     "avg_w": power["avg_w"] if power else None, "pci": my_pci,
                     "comm_ms_exposed": None if comm_ms is None else round(comm_ms, 4),
@@ -586,7 +643,7 @@ def main():
         per_rank = {k: [r[k] for r in recs] for k in mine_rec}
 
     replicas_identical = None
-    if dp and train:     # DDP invariant, checked outside the timed region: every rank holds bit-identical parameters
+    if dp and train and args.full:     # DDP invariant, checked outside the timed region: every rank holds bit-identical parameters
         bits = trainer.flat.view(torch.int32).to(torch.int64)
         h = torch.stack([bits.sum(), (bits * torch.arange(1, bits.numel() + 1, device=dev, dtype=torch.int64)).sum()])   # (wraps: fine, it is a hash)
         hs = [torch.zeros_like(h) for _ in range(world)]
@@ -600,7 +657,7 @@ def main():
 
     # ---- the second half of BASELINE's metric ("PSNR delta vs ref"), outside the timed region, in the mode the line is timed in
     psnr_delta = None
-    if rank == 0 and NF == 32 and not args.no_psnr:
+    if args.full and rank == 0 and NF == 32 and not args.no_psnr:
         psnr_delta = psnr_delta_vs_reference(kind, args.math, dev)
         # north_star names the XMM-SuperRes PSNR: every line carries BOTH generators' figures (psnr.sr_delta_db, psnr.dn_delta_db);
         # the top-level psnr_delta_db stays the timed workload's kind
@@ -612,7 +669,7 @@ def main():
 
     # ---- extra leg (same process, same inputs): another math mode over the same --steps/--warmup, labelled; never the headline
     extra = None
-    xm = None if (args.no_extra or world > 1 or args.extra_math in ("none", args.math)) else args.extra_math   # N=1 only
+    xm = None if (not args.full or args.no_extra or world > 1 or args.extra_math in ("none", args.math)) else args.extra_math   # N=1 only
     if xm is not None:
         with torch.no_grad():
             y_head = model(x[:2]).clone()
@@ -622,7 +679,7 @@ def main():
         err = float((y_x - y_head).abs().max())
         xm = eng.get_math()       # what the kernels really compute in (generic widths run exact fp32 whatever was asked for)
         pwx = PowerWatch(pci=[my_pci] if my_pci else None)
-        dte, _, profe, _ = timed(args.warmup, args.steps, not args.no_profile, pwx)
+        dte, _, profe, _, _ = timed(args.warmup, args.steps, not args.no_profile, pwx)
         extra = {"math": xm, "dtype": MATHS[xm][0], "value": B * world * args.steps / dte, "unit": "tiles/s",
                  "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dte / args.steps,
                  "max_abs_output_diff_vs_" + args.math: err, "note": "not the headline: the strict mode, reported for comparison"}
@@ -663,7 +720,7 @@ def main():
             # the step runs at the package cap, so the rate IS watts / joules per tile: the figure a kernel change has to move
             power["joules_per_tile"] = round(power["avg_w"] * (dt / args.steps) / B, 3)
             out["power"] = power
-        if train:
+        if train and args.full:
             out["comm_ms_exposed"] = None if comm_ms is None else round(comm_ms, 4)     # rank 0's; every rank's in per_rank
         if per_rank is not None:
             out["per_rank"] = per_rank
@@ -671,7 +728,7 @@ def main():
             out.update(psnr_delta)
         if extra is not None:
             out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline and NF == 32:
+        if args.full and world == 1 and not args.no_cpu_baseline and NF == 32:
             out["cpu_baseline"] = cpu_baseline(kind, train, tile=T)      # the same step at the same tile size on the host cores (B = 1)
         print(json.dumps(out), flush=True)
     if dp:

@@ -145,3 +145,32 @@ def test_default_steps_give_a_settled_timed_region():
     k4 = bench.default_steps(4, 416, True, "f16x3")          # the reference's training batch of four: ~22 ms per step
     assert 150 <= k4 <= 300 and 3.0 <= k4 * 0.0217 <= 6.5
     assert bench.default_steps(1, 16, False, "f16x3") == 5000
+
+
+def test_dump_outputs_stay_under_the_limit_with_a_fixed_sample(tmp_path):
+    """bench.write_outputs (--dump-outputs DIR): arrays go out as DIR/<name>.npy in float32 (float64 stays float64); when the files
+    would pass the limit the largest array is replaced by DIR/<name>_sample.npy, the same positions for the same shape on every call,
+    so that two builds' dumps compare element for element."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    big = rng.standard_normal((4, 1, 300, 301)).astype(np.float32)
+    arrays = {"loss": np.float32(0.25), "params": rng.standard_normal(1000).astype(np.float32), "output": big}
+    w = bench.write_outputs(str(tmp_path / "a"), arrays)
+    assert w == {"loss.npy": [], "params.npy": [1000], "output.npy": [4, 1, 300, 301]}
+    o = np.load(tmp_path / "a" / "output.npy")
+    assert o.dtype == np.float32 and np.array_equal(o, big)
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float32
+    assert bench.write_outputs(str(tmp_path / "e"), {"y": big.astype(np.float64)}) == {"y.npy": [4, 1, 300, 301]}
+    limit = 200_000                                          # the output alone is 1.4 MB in float32: sampled
+    w1 = bench.write_outputs(str(tmp_path / "b"), arrays, limit)
+    w2 = bench.write_outputs(str(tmp_path / "c"), {k: (v * 2 if k == "output" else v) for k, v in arrays.items()}, limit)
+    assert set(w1) == {"loss.npy", "params.npy", "output_sample.npy"} and w1 == w2
+    files = [os.path.join(tmp_path, "b", f) for f in w1]
+    assert sum(os.path.getsize(f) for f in files) <= limit
+    s1, s2 = np.load(tmp_path / "b" / "output_sample.npy"), np.load(tmp_path / "c" / "output_sample.npy")
+    assert s1.size == (limit - 4004 - 3 * 128) // 4 and np.array_equal(2 * s1, s2)           # same positions, all the room used
+    assert np.isin(s1, big.reshape(-1)).all()
+    assert np.load(tmp_path / "b" / "params.npy").shape == (1000,)
+    f64 = bench.write_outputs(str(tmp_path / "d"), {"x": np.arange(3.0)})
+    assert f64 == {"x.npy": [3]} and np.load(tmp_path / "d" / "x.npy").dtype == np.float64

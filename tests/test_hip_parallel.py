@@ -111,7 +111,7 @@ def test_bench_one_rank_over_rccl_with_the_reduce_path_forced():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XSD_DIST_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--no-extra", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+                        "--full", "--no-extra", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0, out[-3000:]
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -132,7 +132,7 @@ def test_bench_line_reports_package_power_and_clock():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XSD_DIST_BACKEND", "XSD_FORCE_DP"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--no-extra", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--full", "--no-extra", "--no-cpu-baseline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0, out[-3000:]
@@ -174,7 +174,7 @@ def test_bench_line_at_the_reference_operating_point():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XSD_DIST_BACKEND", "XSD_FORCE_DP"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tile", "416", "--batch", "4", "--steps", "6", "--warmup", "2", "--no-extra",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tile", "416", "--batch", "4", "--steps", "6", "--warmup", "2", "--full", "--no-extra",
                         "--no-sustained", "--no-psnr", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0, out[-3000:]
@@ -189,6 +189,45 @@ def test_bench_line_at_the_reference_operating_point():
     L = _lib.load()
     L.xsd_debug_persistent_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     assert L.xsd_debug_persistent_grid(4 * 26 * 13, 256) == 226 and L.xsd_debug_persistent_grid(26 * 13, 256) == 169
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the steps and prints the headline only; --dump-outputs DIR writes what the last timed
+    step returned: the train step's loss, the parameters after its Adam update and its gradient, the forward's output.  The inputs
+    are seeded, so two runs with the same arguments dump the same arrays."""
+    import json
+    from xmm_superres_denoise.models import GeneratorRRDB_DN
+    root = os.path.dirname(HERE)
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "XSD_DIST_BACKEND", "XSD_FORCE_DP"):
+        env.pop(k, None)
+
+    def run(workload, out):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", workload, "--batch", "2", "--tile", "64",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert p.returncode == 0, (p.stdout + p.stderr).decode(errors="replace")[-3000:]
+        lines = [l for l in p.stdout.decode(errors="replace").splitlines() if l.startswith("{")]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    d = run("dn_train", tmp_path / "a")
+    assert d["metric"] == "XMM 64x64 tiles/sec (train step)" and d["unit"] == "tiles/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and "22-23 significant" in d["dtype"]
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "unprofiled", "power", "psnr_delta_db", "extra", "cpu_baseline", "comm_ms_exposed", "per_rank"):
+        assert k not in d, k
+    npar = sum(p.numel() for p in GeneratorRRDB_DN(1, 1, 32, 4).parameters())
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "params", "grads")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in a.values()) and a["params"].shape == a["grads"].shape == (npar,)
+    assert a["loss"].size == 1 and 0.05 < float(a["loss"].reshape(-1)[0]) < 2.0 and np.isfinite(a["grads"]).all() and np.abs(a["grads"]).max() > 0
+    run("dn_train", tmp_path / "b")
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{n}.npy")), n
+    f = run("dn_fwd", tmp_path / "f")
+    assert f["metric"] == "XMM 64x64 tiles/sec (forward)" and "roofline" not in f
+    y = np.load(tmp_path / "f" / "output.npy")
+    assert y.shape == (2, 1, 64, 64) and y.dtype == np.float32 and np.isfinite(y).all()
 
 
 def test_train_driver_one_rank_over_rccl(tmp_path):
@@ -230,7 +269,7 @@ def test_bench_n_ranks_gloo_on_one_gpu(world):
     if torch.cuda.device_count() < world:
         env["XSD_DIST_BACKEND"] = "gloo"
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--no-extra", "--no-cpu-baseline", "--sustained-seconds", "0.2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+                        "--full", "--no-extra", "--no-cpu-baseline", "--sustained-seconds", "0.2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     out = p.stdout.decode(errors="replace")
     assert p.returncode == 0, out[-3000:]
     lines = [l for l in out.splitlines() if l.startswith("{")]

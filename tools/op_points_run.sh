@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/op6; mkdir -p $O
 cd $R
 python3 tools/operating_points.py --seconds 1.0 --out $O/r06_operating_points_before.txt > $O/op.log 2>&1 || { tail -20 $O/op.log; exit 1; }
 echo "matrix done"
-python3 bench.py --workload dn_train --batch 4 --tile 416 --steps 20 --warmup 3 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/bench_dn_train_b4_416.json 2> $O/bench_b4.err || exit 1
+python3 bench.py --full --workload dn_train --batch 4 --tile 416 --steps 20 --warmup 3 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/bench_dn_train_b4_416.json 2> $O/bench_b4.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 for C in "dn_fwd 1 416 100" "dn_train 4 416 20" "dn_train 8 416 10" "sr_fwd 1 416 100"; do
   set -- $C

@@ -20,8 +20,8 @@ fmt='
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d["roofline"]
 print(TAG, round(d["value"], 1), "tiles/s", round(d["ms_per_step"], 1), "ms/step  conv", round(r["avg_launch_ms"], 3), "ms x", r["launches"] // d["steps"], " wgrad", round(r["wgrad_kernel"]["avg_launch_ms"], 3), "ms x", r["wgrad_kernel"]["launches"] // d["steps"], d.get("power"))'
-python bench.py --math bf16x6 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-psnr --no-sustained 2>/dev/null | python -c "TAG='dn_train bf16x6'$fmt" >> $O
+python bench.py --full --math bf16x6 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-psnr --no-sustained 2>/dev/null | python -c "TAG='dn_train bf16x6'$fmt" >> $O
 if [ -f xmm-superres-denoise_amd/lib/libxsd_hip_nomfma_strict.so ]; then
-  XSD_LIB=$PWD/xmm-superres-denoise_amd/lib/libxsd_hip_nomfma_strict.so python bench.py --math bf16x6 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-psnr --no-sustained 2>/dev/null | python -c "TAG='dn_train bf16x6 without MFMAs'$fmt" >> $O
+  XSD_LIB=$PWD/xmm-superres-denoise_amd/lib/libxsd_hip_nomfma_strict.so python bench.py --full --math bf16x6 --steps 20 --warmup 5 --no-cpu-baseline --no-extra --no-psnr --no-sustained 2>/dev/null | python -c "TAG='dn_train bf16x6 without MFMAs'$fmt" >> $O
 fi
 cat $O

@@ -32,22 +32,22 @@ cd $R
 fi
 if [[ $PART == *2* ]]; then
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/bench_default.err || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_default.json 2> $O/bench_default.err || exit 1
 # the by-construction-fp32 mode as a first-class line of its own (headline slot, own cpu_baseline; its PMC traffic file is above)
-python3 bench.py --math bf16x6 --no-extra --steps 20 --warmup 5 > $O/${TAG}_bench_bf16x6.json 2> $O/bench_bf16x6.err || exit 1
-python3 bench.py --workload sr_fwd --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sr_fwd.json 2>/dev/null || exit 1
-python3 bench.py --workload dn_fwd --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_dn_fwd.json 2>/dev/null || exit 1
-python3 bench.py --workload sr_train --steps 4 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_sr_train.json 2>/dev/null || exit 1
-python3 bench.py --loss paper --steps 4 --warmup 1 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_paper_loss.json 2>/dev/null || exit 1
-python3 bench.py --input-pipeline --batch 16 --steps 4 --warmup 1 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_input_pipeline_b16.json 2>/dev/null || exit 1
-python3 bench.py --batch 16 --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_b16.json 2>/dev/null || exit 1
+python3 bench.py --full --math bf16x6 --no-extra --steps 20 --warmup 5 > $O/${TAG}_bench_bf16x6.json 2> $O/bench_bf16x6.err || exit 1
+python3 bench.py --full --workload sr_fwd --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sr_fwd.json 2>/dev/null || exit 1
+python3 bench.py --full --workload dn_fwd --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_dn_fwd.json 2>/dev/null || exit 1
+python3 bench.py --full --workload sr_train --steps 4 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_sr_train.json 2>/dev/null || exit 1
+python3 bench.py --full --loss paper --steps 4 --warmup 1 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_paper_loss.json 2>/dev/null || exit 1
+python3 bench.py --full --input-pipeline --batch 16 --steps 4 --warmup 1 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_input_pipeline_b16.json 2>/dev/null || exit 1
+python3 bench.py --full --batch 16 --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-sustained --no-psnr > $O/${TAG}_bench_dn_train_b16.json 2>/dev/null || exit 1
 # the RCCL code path on the one GPU: a one-rank nccl process group with the reduce path forced on (parallel.collectives_on)
-XSD_FORCE_DP=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python3 bench.py --gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-sustained --no-psnr 2> $O/dp1_rccl.err | grep '^{' > $O/${TAG}_bench_dp1_rccl_one_gpu.json || exit 1      # (RCCL / gloo print banners on stdout: the .json holds the line only)
-XSD_DIST_BACKEND=gloo python3 bench.py --gpus 2 --batch 8 --steps 3 --warmup 1 --no-extra 2> $O/dp2.err | grep '^{' > $O/${TAG}_bench_dp2_gloo_one_gpu.json || exit 1
+XSD_FORCE_DP=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 python3 bench.py --full --gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-extra --no-sustained --no-psnr 2> $O/dp1_rccl.err | grep '^{' > $O/${TAG}_bench_dp1_rccl_one_gpu.json || exit 1      # (RCCL / gloo print banners on stdout: the .json holds the line only)
+XSD_DIST_BACKEND=gloo python3 bench.py --full --gpus 2 --batch 8 --steps 3 --warmup 1 --no-extra 2> $O/dp2.err | grep '^{' > $O/${TAG}_bench_dp2_gloo_one_gpu.json || exit 1
 # round 6: the reference's own operating points (batch 1 / 4 / 8, 416 x 416): lines with roofline / edge blocks, then the whole matrix
-python3 bench.py --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_dn_train_b4_416.json 2>/dev/null || exit 1
-python3 bench.py --workload sr_train --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline --no-extra > $O/${TAG}_bench_sr_train_b4_416.json 2>/dev/null || exit 1
-python3 bench.py --workload sr_fwd --batch 1 --tile 416 --steps 200 --warmup 10 --no-cpu-baseline --no-extra > $O/${TAG}_bench_sr_fwd_b1_416.json 2>/dev/null || exit 1
+python3 bench.py --full --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_dn_train_b4_416.json 2>/dev/null || exit 1
+python3 bench.py --full --workload sr_train --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline --no-extra > $O/${TAG}_bench_sr_train_b4_416.json 2>/dev/null || exit 1
+python3 bench.py --full --workload sr_fwd --batch 1 --tile 416 --steps 200 --warmup 10 --no-cpu-baseline --no-extra > $O/${TAG}_bench_sr_fwd_b1_416.json 2>/dev/null || exit 1
 python3 tools/operating_points.py --seconds 1.5 --out $O/${TAG}_operating_points.txt > $O/operating_points.log 2>&1 || exit 1
 ./tools/bin/launch_floor_probe > $O/${TAG}_launch_floor.txt 2>&1 || exit 1
 for c in "1 416" "1 512" "4 416" "32 512"; do XSD_LIB=$R/xmm-superres-denoise_amd/lib/libxsd_hip_diag.so python3 tools/stamps_small.py f16x3 $c >> $O/${TAG}_small_grid_stamps.txt 2>/dev/null || exit 1; done

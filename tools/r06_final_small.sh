@@ -5,10 +5,10 @@ python -m pytest tests/test_hip_kernels.py tests/test_hip_network.py tests/test_
 tail -2 $O/pytest_subset.log
 python3 tools/operating_points.py --seconds 1.5 --out $O/r06_operating_points.txt > $O/operating_points.log 2>&1 || exit 1
 echo matrix done
-python3 bench.py --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_dn_train_b4_416.json 2>/dev/null || exit 1
-python3 bench.py --workload sr_train --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline --no-extra > $O/r06_bench_sr_train_b4_416.json 2>/dev/null || exit 1
-python3 bench.py --workload sr_fwd --batch 1 --tile 416 --steps 200 --warmup 10 --no-cpu-baseline --no-extra > $O/r06_bench_sr_fwd_b1_416.json 2>/dev/null || exit 1
-python3 bench.py --batch 1 --tile 416 --steps 100 --warmup 10 --no-cpu-baseline --no-extra > $O/r06_bench_dn_train_b1_416.json 2>/dev/null || exit 1
+python3 bench.py --full --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline > $O/r06_bench_dn_train_b4_416.json 2>/dev/null || exit 1
+python3 bench.py --full --workload sr_train --batch 4 --tile 416 --steps 40 --warmup 5 --no-cpu-baseline --no-extra > $O/r06_bench_sr_train_b4_416.json 2>/dev/null || exit 1
+python3 bench.py --full --workload sr_fwd --batch 1 --tile 416 --steps 200 --warmup 10 --no-cpu-baseline --no-extra > $O/r06_bench_sr_fwd_b1_416.json 2>/dev/null || exit 1
+python3 bench.py --full --batch 1 --tile 416 --steps 100 --warmup 10 --no-cpu-baseline --no-extra > $O/r06_bench_dn_train_b1_416.json 2>/dev/null || exit 1
 echo lines done
 cd /tmp && export TMPDIR=/tmp
 for C in "dn_train 4 416 20" "dn_fwd 1 416 100" "dn_train 1 416 60"; do
