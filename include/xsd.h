@@ -176,6 +176,41 @@ int xsd_normalize(const float* dev_in, float* dev_out, int64_t n, float max_val,
 /* ImageUpsample: nearest x scale then / scale^2 (transforms/imageupsample.py:10-26); in [N][H][W] */
 int xsd_image_upsample(const float* dev_in, float* dev_out, int N, int H, int W, int scale, void* stream);
 
+/* ---- Restormer denoiser, forward only (csrc/restormer.hip) ---------------------------------------------------
+ * The reference's Restormer (models/transformer/restormer.py:217-406; factory models/model.py:226-234, XMM configuration
+ * res/configs/models.toml:58-64: dim = 24, 1 -> 1 channels).  Exact fp32 on the vector ALUs; xsd_set_math does not apply.
+ * Reductions over an image (the channel attention's row norms and Gram) are fixed-order partial sums: outputs are bitwise
+ * reproducible and each image's output is independent of the batch it is computed in.  No backward: training Restormer is not
+ * on this engine.
+ * Flat parameter layout: fp32, the reference's state_dict order (patch_embed.proj.weight, encoder_level1.{i}.{norm1.body.weight,
+ * norm1.body.bias, attn.temperature, attn.qkv.*, attn.qkv_dwconv.*, attn.project_out.*, norm2.*, ffn.project_in.*, ffn.dwconv.*,
+ * ffn.project_out.*}, down1_2.body.0.weight, ..., output.weight[, output.bias]; biases of the convs only when bias != 0,
+ * norm*.body.bias only for WithBias). */
+typedef struct xsd_restormer xsd_restormer;
+typedef struct xsd_restormer_config {   /* Restormer.__init__ arguments (restormer.py:218-230) */
+    int32_t inp_channels;          /* 1..1024 */
+    int32_t out_channels;          /* must equal inp_channels: `output(x) + inp_img` (:404) */
+    int32_t dim;                   /* even, 2..1024 (Downsample halves it, :188) */
+    int32_t num_blocks[4];         /* 0..64 each */
+    int32_t num_refinement_blocks; /* 0..64 */
+    int32_t heads[4];              /* heads[l] divides dim * 2^l (heads[0] also 2 dim) into at most 64 channels per head */
+    int32_t bias;                  /* 0/1: conv biases */
+    int32_t layernorm_bias_free;   /* 0 = "WithBias", 1 = "BiasFree" (:61-73) */
+    int32_t dual_pixel_task;       /* must be 0 (refused) */
+    double ffn_expansion_factor;   /* hidden width of a level with C channels = (int)(C * factor) (:82) */
+} xsd_restormer_config;
+/* replaces Restormer.__init__ (engine state only; weights stay in the caller's flat buffer) */
+int xsd_restormer_create(const xsd_restormer_config* cfg, xsd_restormer** out);
+void xsd_restormer_destroy(xsd_restormer* r);
+int64_t xsd_restormer_param_count(const xsd_restormer* r);
+/* the engine's weight-layout step (1x1 conv weights transposed to [cin][cout]); after every parameter update, before forward.
+ * The engine keeps reading dev_params (LayerNorm, temperature, depthwise and 3x3 weights, biases) until the next pack. */
+int xsd_restormer_pack_weights(xsd_restormer* r, const float* dev_params, void* stream);
+/* replaces Restormer.forward (restormer.py:368-406; no clamp there -- Model.forward clamps, models/model.py:48-49).
+ * x: [B][inp_channels][H][W], y: [B][out_channels][H][W], H and W divisible by 8 (three PixelUnshuffle(2) levels), B >= 1.
+ * A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
+int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

@@ -50,6 +50,13 @@ static int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
+namespace xsd {
+int set_last_error(int code, const std::string& msg)      // for the other translation units of the library (restormer.hip)
+{
+    g_err = msg;
+    return code;
+}
+} // namespace xsd
 #define HIPCHK(expr)                                                                                      \
     do {                                                                                                  \
         hipError_t _e = (expr);                                                                           \

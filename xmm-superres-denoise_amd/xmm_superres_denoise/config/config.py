@@ -1,7 +1,7 @@
 """The slice of the reference's pydantic config that defines the constructor-API contract of the hot path
 (reference config/config.py:36-42,164-203).  Python 3.10 here: enum.StrEnum restated as (str, Enum)."""
 from enum import Enum
-from typing import Literal, Tuple
+from typing import Literal, Tuple, Union
 
 from pydantic import BaseModel, Field, NonNegativeFloat, PositiveInt, model_validator
 
@@ -31,20 +31,30 @@ class RrdbCfg(BaseModel):
     residual_blocks: PositiveInt
 
 
+class RestormerCfg(BaseModel):
+    """reference config/config.py:187-191"""
+    base_model: Literal["restormer"]
+    in_channels: PositiveInt
+    out_channels: PositiveInt
+    dim: PositiveInt
+
+
 class ModelCfg(BaseModel):
     name: BaseModels
     memory_efficient: bool
     batch_size: PositiveInt
-    model: RrdbCfg  # reference: RrdbCfg | TransformerCfg | RestormerCfg (transformer zoo is off the hot path)
+    # reference: RrdbCfg | TransformerCfg | RestormerCfg (the timm-based transformer zoo -- SwinFIR, DRCT, HAT -- is off the engine)
+    model: Union[RrdbCfg, RestormerCfg] = Field(..., discriminator="base_model")
     optimizer: OptimizerCfg
 
 
-# res/configs/models.toml:1-17 of the reference (the two shipped RRDB models)
+# res/configs/models.toml:1-17 and :58-64 of the reference (the two shipped RRDB models and the Restormer denoiser)
 MODELS_TOML = {
     "esr_gen": dict(base_model="esr_gen", in_channels=1, out_channels=1, filters=32, residual_blocks=4,
                     learning_rate=0.0001, betas=(0.9, 0.999)),
     "rrdb_denoise": dict(base_model="rrdb_denoise", in_channels=1, out_channels=1, filters=32, residual_blocks=4,
                          learning_rate=0.0001, betas=(0.9, 0.999)),
+    "restormer": dict(base_model="restormer", in_channels=1, out_channels=1, dim=24, learning_rate=0.0001, betas=(0.9, 0.999)),
 }
 
 
@@ -54,8 +64,8 @@ def model_cfg(name: str, batch_size: int = 1, memory_efficient: bool = False, **
     d = dict(MODELS_TOML[name])
     d.update(overrides)
     opt = OptimizerCfg(learning_rate=d.pop("learning_rate"), betas=tuple(d.pop("betas")))
-    return ModelCfg(name=BaseModels(name), memory_efficient=memory_efficient, batch_size=batch_size,
-                    model=RrdbCfg(**d), optimizer=opt)
+    cfg = RestormerCfg(**d) if d["base_model"] == "restormer" else RrdbCfg(**d)
+    return ModelCfg(name=BaseModels(name), memory_efficient=memory_efficient, batch_size=batch_size, model=cfg, optimizer=opt)
 
 
 class ConfigError(Exception):

@@ -22,6 +22,13 @@ class XsdConfig(ctypes.Structure):
                  "memory_efficient", "reserved")]
 
 
+class XsdRestormerConfig(ctypes.Structure):
+    _fields_ = [("inp_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("dim", ctypes.c_int32),
+                ("num_blocks", ctypes.c_int32 * 4), ("num_refinement_blocks", ctypes.c_int32), ("heads", ctypes.c_int32 * 4),
+                ("bias", ctypes.c_int32), ("layernorm_bias_free", ctypes.c_int32), ("dual_pixel_task", ctypes.c_int32),
+                ("ffn_expansion_factor", ctypes.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -73,6 +80,13 @@ def load():
     L.xsd_probe_mfma_stream.argtypes = [i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp]
     L.xsd_test_conv3x3.argtypes = [vp, ctypes.POINTER(vp), i32, fp, fp, ctypes.POINTER(vp), i32, f32, i32, i32, i32, vp]
     L.xsd_test_conv3x3_bwd.argtypes = [vp, ctypes.POINTER(vp), i32, fp, fp, ctypes.POINTER(vp), fp, fp, i32, i32, i32, vp]
+    L.xsd_restormer_create.argtypes = [ctypes.POINTER(XsdRestormerConfig), ctypes.POINTER(vp)]
+    L.xsd_restormer_destroy.argtypes = [vp]
+    L.xsd_restormer_destroy.restype = None
+    L.xsd_restormer_param_count.argtypes = [vp]
+    L.xsd_restormer_param_count.restype = i64
+    L.xsd_restormer_pack_weights.argtypes = [vp, fp, vp]
+    L.xsd_restormer_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
     _lib = L
     return L
 
@@ -83,6 +97,7 @@ ABI_SYMBOLS = [
     "xsd_forward", "xsd_backward", "xsd_backward_num_stages", "xsd_backward_stage", "xsd_grad_range",
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_normalize", "xsd_image_upsample",
     "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd",
+    "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
 ]
 
 

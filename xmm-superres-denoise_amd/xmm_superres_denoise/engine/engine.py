@@ -206,6 +206,50 @@ class Engine:
         return {"mfma_tflops": tf.value, "sclk_ghz": gz.value, "seconds": float(seconds), "fmt": fmt}
 
 
+class RestormerEngine:
+    """One Restormer engine per module per GPU (xsd_restormer_create / _destroy): forward only."""
+
+    def __init__(self, inp_channels: int, out_channels: int, dim: int, num_blocks, num_refinement_blocks: int, heads,
+                 ffn_expansion_factor: float, bias: bool, layernorm_bias_free: bool):
+        self.L = _lib.load()
+        cfg = _lib.XsdRestormerConfig(inp_channels=inp_channels, out_channels=out_channels, dim=dim,
+                                      num_blocks=(ctypes.c_int32 * 4)(*num_blocks), num_refinement_blocks=num_refinement_blocks,
+                                      heads=(ctypes.c_int32 * 4)(*heads), bias=int(bias), layernorm_bias_free=int(layernorm_bias_free),
+                                      dual_pixel_task=0, ffn_expansion_factor=float(ffn_expansion_factor))
+        h = ctypes.c_void_p()
+        check(self.L.xsd_restormer_create(ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+        self.in_channels, self.out_channels = int(inp_channels), int(out_channels)
+        self.nparams = int(self.L.xsd_restormer_param_count(self.h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.xsd_restormer_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @_on_engine_device
+    def pack(self, flat_params: torch.Tensor):
+        _require_cuda_f32(flat_params, "flat_params")
+        if flat_params.numel() != self.nparams:
+            raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
+        self._params_ref = flat_params  # keep alive: the engine reads norms, depthwise / 3x3 weights and biases from it
+        check(self.L.xsd_restormer_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
+
+    @_on_engine_device
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _require_cuda_f32(x, "x")
+        if x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise XsdError(f"x must be [B,{self.in_channels},H,W] (got {tuple(x.shape)})")
+        B, _, H, W = x.shape
+        y = torch.empty((B, self.out_channels, H, W), device=x.device, dtype=torch.float32)
+        check(self.L.xsd_restormer_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
+        return y
+
+
 # ---- stateless transform entry points --------------------------------------------------------------------------
 @_on_tensor_device
 def mask_pad_normalize(counts: torch.Tensor, mask: torch.Tensor | None, res: int, max_val: float | None,

@@ -1,4 +1,5 @@
-"""`Model`: the reference's LightningModule (models/model.py:13-247) restated without Lightning for the RRDB paths:
+"""`Model`: the reference's LightningModule (models/model.py:13-247) restated without Lightning for the RRDB paths and the
+Restormer forward:
 constructor signature, `configure_model` factory (model.py:153-186), `forward` = clamp(generator(x), 0, 1)
 (model.py:48-49 -- the second clamp is fused in the engine's output kernel and is idempotent), `_on_step` / `_on_epoch_end` (model.py:72-150, returning what the reference logs) and `configure_optimizers`
 (model.py:239-247).
@@ -48,13 +49,16 @@ class Model(nn.Module):
     def forward(self, x) -> torch.Tensor:
         if self.model is None:
             self.configure_model()
+        if BaseModels(self.config.name) is BaseModels.RESTORMER:
+            # the reference clamps here (model.py:48-49); Restormer itself does not (restormer.py:404)
+            return torch.clamp(self.model(x), min=0.0, max=1.0)
         # the generator already returns clamp(clamp(.)) == clamp(.)
         return self.model(x)
 
     def configure_model(self) -> None:
         if self.model is not None:
             return
-        from xmm_superres_denoise.models import GeneratorRRDB_DN, GeneratorRRDB_SR
+        from xmm_superres_denoise.models import GeneratorRRDB_DN, GeneratorRRDB_SR, Restormer
         name = BaseModels(self.config.name)
         if name is BaseModels.ESR_GEN:
             up_scale = self.hr_shape[0] / self.lr_shape[0]
@@ -73,8 +77,13 @@ class Model(nn.Module):
                                           num_filters=self.config.model.filters,
                                           num_res_blocks=self.config.model.residual_blocks,
                                           memory_efficient=self.config.memory_efficient)
+        elif name is BaseModels.RESTORMER:
+            # reference model.py:226-234: only the channel counts and dim come from the config; forward only on this engine
+            self.model = Restormer(inp_channels=self.config.model.in_channels, out_channels=self.config.model.out_channels,
+                                   dim=self.config.model.dim)
         else:
-            raise NotImplementedError(f"{name}: only the RRDB generators are on the MI355X hot path (SURVEY.md section 8)")
+            raise NotImplementedError(f"{name}: only the RRDB generators and Restormer are on the MI355X engine (SURVEY.md section 8; "
+                                      "SwinFIR, DRCT and HAT need timm)")
 
     def training_step(self, batch, batch_idx=0):
         return self._on_step(batch, "train")

@@ -61,6 +61,9 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
         loss: str = "l1", scaling: str = "linear", val_batches: int = 0):
     """loss: "l1" (BASELINE configs[2]) or "paper" = the reference's shipped default, 0.5 psnr + 0.5 ms_ssim with the
     scaling table of the dataset's stretch mode (`scaling`; res/configs/loss_functions.toml, train.py:46-63)."""
+    if name == "restormer":
+        raise NotImplementedError("restormer: training Restormer is not on the MI355X engine (forward only: inference, infer.py, "
+                                  "validation / test metrics); fit supports rrdb_denoise and esr_gen")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -130,7 +133,8 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
 def main():
     ap = argparse.ArgumentParser(description="fit an RRDB generator on synthetic tiles with the MI355X engine")
     ap.add_argument("routine", choices=["fit"])
-    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen"])
+    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer"],
+                    help="restormer is refused: forward only on this engine")
     ap.add_argument("--lr-res", type=int, default=416)
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
