@@ -211,6 +211,54 @@ int xsd_restormer_pack_weights(xsd_restormer* r, const float* dev_params, void* 
  * A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
 int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
 
+/* ---- SwinFIR super-resolution, forward only (csrc/swinfir.hip) ----------------------------------------------
+ * The reference's SwinFIR (models/transformer/swinfir.py:120-441 with the Swin blocks of modules.py; factory models/model.py:187-200,
+ * XMM configuration res/configs/models.toml [swinfir]: img_size 416, patch_size 32, window_size 16 -> an effective window of 13 without
+ * shift, embed_dim 180, 6 x 6 blocks of 6 heads, in_chans 1, upscale 2).  Eval-mode forward in exact fp32: the linear layers, the
+ * window attention and the 3x3 convs on the fp32 MFMA, the FourierUnit's FFTs on the vector ALUs; xsd_set_math does not apply.  No
+ * float atomics: outputs are bitwise reproducible and each image's output is independent of the batch it is computed in.
+ * Flat parameter layout: fp32, the order of SwinFIR.parameters() (conv_first.*, patch_embed.norm.* (patch_norm), per layer i and
+ * block j layers.i.residual_group.blocks.j.{norm1.*, attn.relative_position_bias_table, attn.qkv.weight[, .bias], attn.proj.*, norm2.*,
+ * mlp.fc1.*, mlp.fc2.*}, then layers.i.conv.* (SFB: S.body.0, S.body.2, F.conv1.0, F.fu.conv_layer, F.conv2, fusion; 1conv: the conv),
+ * norm.*, conv_after_body.*, conv_before_upsample.0.*, upsample.{0,2,..}.*, conv_last.*).  The buffers relative_position_index and
+ * attn_mask are not in it: the engine computes both from the configuration. */
+typedef struct xsd_swinfir xsd_swinfir;
+typedef struct xsd_swinfir_config {   /* SwinFIR.__init__ arguments (swinfir.py:291-313) */
+    int32_t img_size[2];           /* (H, W); with patch_size it sets the effective window: min(img // patch) if <= window_size */
+    int32_t patch_size[2];
+    int32_t in_chans;              /* 1..64 (3: the reference subtracts its RGB mean) */
+    int32_t embed_dim;             /* 2..4096 */
+    int32_t num_layers;            /* 0..16 */
+    int32_t depths[16];            /* 0..64 each */
+    int32_t num_heads[16];         /* divides embed_dim into at most 32 channels per head */
+    int32_t window_size;           /* the effective window must be <= 16 */
+    int32_t qkv_bias;              /* 0/1 */
+    int32_t ape;                   /* must be 0 (refused) */
+    int32_t patch_norm;            /* 0/1 */
+    int32_t upscale;               /* 2, 3, 4, 8 */
+    int32_t upsampler;             /* 0 = "pixelshuffle" (the only one supported); 1 "pixelshuffledirect", 2 "nearest+conv", 3 "" are refused */
+    int32_t resi_connection;       /* 0 = "SFB", 1 = "1conv"; 2 "HSFB", 3 "identity" are refused */
+    double mlp_ratio;              /* hidden width (int)(embed_dim * mlp_ratio) */
+    double qk_scale;               /* 0: head_dim^-0.5 (the reference's `qk_scale or ...`); > 0 as given; < 0 refused */
+    double img_range;              /* > 0 */
+} xsd_swinfir_config;
+/* replaces SwinFIR.__init__ (engine state only; weights stay in the caller's flat buffer) */
+int xsd_swinfir_create(const xsd_swinfir_config* cfg, xsd_swinfir** out);
+void xsd_swinfir_destroy(xsd_swinfir* r);
+int64_t xsd_swinfir_param_count(const xsd_swinfir* r);
+/* the engine's weight-layout step (Linear / conv weights to [taps][cin][cout]); after every parameter update, before forward.
+ * The engine keeps reading dev_params (LayerNorms, bias tables, biases) until the next pack. */
+int xsd_swinfir_pack_weights(xsd_swinfir* r, const float* dev_params, void* stream);
+/* replaces SwinFIR.forward (swinfir.py:420-441; no clamp there -- Model.forward clamps, models/model.py:48-49).
+ * x: [B][in_chans][H][W], y: [B][in_chans][upscale H][upscale W]; H and W multiples of the effective window and, with SFB, FFT sizes
+ * (<= 4096, prime factors <= 13).  A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
+int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* 1 if the FourierUnit's FFT takes a length of n, else 0 */
+int xsd_swinfir_fft_supported(int n);
+/* the FourierUnit's transform pair on its own: x [B][H][W][C2] (token-major real) -> spec [B][H][W/2+1][2 C2] (re, im interleaved)
+ * = rfftn(x, norm="ortho"); with inverse set, x += irfftn(spec, s=(H, W), norm="ortho") and spec is overwritten. */
+int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, int H, int W, int C2, int inverse, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

@@ -1,7 +1,7 @@
 """The slice of the reference's pydantic config that defines the constructor-API contract of the hot path
 (reference config/config.py:36-42,164-203).  Python 3.10 here: enum.StrEnum restated as (str, Enum)."""
 from enum import Enum
-from typing import Literal, Tuple, Union
+from typing import List, Literal, Tuple, Union
 
 from pydantic import BaseModel, Field, NonNegativeFloat, PositiveInt, model_validator
 
@@ -39,21 +39,42 @@ class RestormerCfg(BaseModel):
     dim: PositiveInt
 
 
+class TransformerCfg(BaseModel):
+    """reference config/config.py:177-186"""
+    base_model: Literal["swinfir", "drct", "hat"]
+    patch_size: PositiveInt
+    img_size: PositiveInt
+    window_size: PositiveInt
+    embed_dim: PositiveInt
+    upsampler: Literal["pixelshuffle", "pixelshuffledirect", "nearest+conv", ""]
+    in_channels: PositiveInt
+    num_heads: List[PositiveInt]
+    depths: List[PositiveInt]
+
+
 class ModelCfg(BaseModel):
     name: BaseModels
     memory_efficient: bool
     batch_size: PositiveInt
-    # reference: RrdbCfg | TransformerCfg | RestormerCfg (the timm-based transformer zoo -- SwinFIR, DRCT, HAT -- is off the engine)
-    model: Union[RrdbCfg, RestormerCfg] = Field(..., discriminator="base_model")
+    # reference: RrdbCfg | TransformerCfg | RestormerCfg (of the TransformerCfg models, SwinFIR runs on the engine; DRCT and HAT
+    # are refused by Model.configure_model)
+    model: Union[RrdbCfg, TransformerCfg, RestormerCfg] = Field(..., discriminator="base_model")
     optimizer: OptimizerCfg
 
 
-# res/configs/models.toml:1-17 and :58-64 of the reference (the two shipped RRDB models and the Restormer denoiser)
+# res/configs/models.toml of the reference: the two shipped RRDB models, SwinFIR, DRCT, HAT and the Restormer denoiser
 MODELS_TOML = {
     "esr_gen": dict(base_model="esr_gen", in_channels=1, out_channels=1, filters=32, residual_blocks=4,
                     learning_rate=0.0001, betas=(0.9, 0.999)),
     "rrdb_denoise": dict(base_model="rrdb_denoise", in_channels=1, out_channels=1, filters=32, residual_blocks=4,
                          learning_rate=0.0001, betas=(0.9, 0.999)),
+    "swinfir": dict(base_model="swinfir", img_size=416, window_size=16, patch_size=32, embed_dim=180, upsampler="pixelshuffle",
+                    in_channels=1, num_heads=[6, 6, 6, 6, 6, 6], depths=[6, 6, 6, 6, 6, 6], learning_rate=0.0002, betas=(0.9, 0.999)),
+    # :32-56 -- configurable, but Model.configure_model refuses both (DRCT's body is dead code in the reference; HAT is not built)
+    "drct": dict(base_model="drct", img_size=416, window_size=16, patch_size=32, embed_dim=180, upsampler="pixelshuffle",
+                 in_channels=1, num_heads=[6, 6, 6, 6, 6, 6], depths=[6, 6, 6, 6, 6, 6], learning_rate=0.0002, betas=(0.9, 0.999)),
+    "hat": dict(base_model="hat", img_size=416, window_size=16, patch_size=16, embed_dim=180, upsampler="pixelshuffle",
+                in_channels=1, num_heads=[6, 6, 6, 6, 6, 6], depths=[6, 6, 6, 6, 6, 6], learning_rate=0.0002, betas=(0.9, 0.999)),
     "restormer": dict(base_model="restormer", in_channels=1, out_channels=1, dim=24, learning_rate=0.0001, betas=(0.9, 0.999)),
 }
 
@@ -64,7 +85,8 @@ def model_cfg(name: str, batch_size: int = 1, memory_efficient: bool = False, **
     d = dict(MODELS_TOML[name])
     d.update(overrides)
     opt = OptimizerCfg(learning_rate=d.pop("learning_rate"), betas=tuple(d.pop("betas")))
-    cfg = RestormerCfg(**d) if d["base_model"] == "restormer" else RrdbCfg(**d)
+    kind = {"restormer": RestormerCfg, "swinfir": TransformerCfg, "drct": TransformerCfg, "hat": TransformerCfg}
+    cfg = kind.get(d["base_model"], RrdbCfg)(**d)
     return ModelCfg(name=BaseModels(name), memory_efficient=memory_efficient, batch_size=batch_size, model=cfg, optimizer=opt)
 
 

@@ -29,6 +29,15 @@ class XsdRestormerConfig(ctypes.Structure):
                 ("ffn_expansion_factor", ctypes.c_double)]
 
 
+class XsdSwinFIRConfig(ctypes.Structure):
+    _fields_ = [("img_size", ctypes.c_int32 * 2), ("patch_size", ctypes.c_int32 * 2), ("in_chans", ctypes.c_int32),
+                ("embed_dim", ctypes.c_int32), ("num_layers", ctypes.c_int32), ("depths", ctypes.c_int32 * 16),
+                ("num_heads", ctypes.c_int32 * 16), ("window_size", ctypes.c_int32), ("qkv_bias", ctypes.c_int32), ("ape", ctypes.c_int32),
+                ("patch_norm", ctypes.c_int32), ("upscale", ctypes.c_int32), ("upsampler", ctypes.c_int32),
+                ("resi_connection", ctypes.c_int32), ("mlp_ratio", ctypes.c_double), ("qk_scale", ctypes.c_double),
+                ("img_range", ctypes.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -87,6 +96,15 @@ def load():
     L.xsd_restormer_param_count.restype = i64
     L.xsd_restormer_pack_weights.argtypes = [vp, fp, vp]
     L.xsd_restormer_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
+    L.xsd_swinfir_create.argtypes = [ctypes.POINTER(XsdSwinFIRConfig), ctypes.POINTER(vp)]
+    L.xsd_swinfir_destroy.argtypes = [vp]
+    L.xsd_swinfir_destroy.restype = None
+    L.xsd_swinfir_param_count.argtypes = [vp]
+    L.xsd_swinfir_param_count.restype = i64
+    L.xsd_swinfir_pack_weights.argtypes = [vp, fp, vp]
+    L.xsd_swinfir_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
+    L.xsd_swinfir_fft_supported.argtypes = [i32]
+    L.xsd_swinfir_test_fft.argtypes = [vp, fp, fp, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 
@@ -98,6 +116,8 @@ ABI_SYMBOLS = [
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_normalize", "xsd_image_upsample",
     "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
+    "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
+    "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft",
 ]
 
 

@@ -250,6 +250,83 @@ class RestormerEngine:
         return y
 
 
+class SwinFIREngine:
+    """One SwinFIR engine per module per GPU (xsd_swinfir_create / _destroy): forward only."""
+
+    UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
+    RESI = ("SFB", "1conv", "HSFB", "identity")
+
+    def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
+                 qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
+                 resi_connection: str):
+        self.L = _lib.load()
+        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
+        if len(depths) > 16 or len(num_heads) < len(depths):
+            raise XsdError(f"SwinFIR: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
+        cfg = _lib.XsdSwinFIRConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
+                                    in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
+                                    depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
+                                    window_size=int(window_size), qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)),
+                                    patch_norm=int(bool(patch_norm)), upscale=int(upscale),
+                                    upsampler=self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3,
+                                    resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 3,
+                                    mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range))
+        h = ctypes.c_void_p()
+        check(self.L.xsd_swinfir_create(ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+        self.in_chans, self.upscale = int(in_chans), int(upscale)
+        self.nparams = int(self.L.xsd_swinfir_param_count(self.h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.xsd_swinfir_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @_on_engine_device
+    def pack(self, flat_params: torch.Tensor):
+        _require_cuda_f32(flat_params, "flat_params")
+        if flat_params.numel() != self.nparams:
+            raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
+        self._params_ref = flat_params  # keep alive: the engine reads norms, bias tables and biases from it
+        check(self.L.xsd_swinfir_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
+
+    @_on_engine_device
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _require_cuda_f32(x, "x")
+        if x.dim() != 4 or x.shape[1] != self.in_chans:
+            raise XsdError(f"x must be [B,{self.in_chans},H,W] (got {tuple(x.shape)})")
+        B, _, H, W = x.shape
+        s = self.upscale
+        y = torch.empty((B, self.in_chans, H * s, W * s), device=x.device, dtype=torch.float32)
+        check(self.L.xsd_swinfir_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
+        return y
+
+    @_on_engine_device
+    def fourier_pair(self, x: torch.Tensor, spec: torch.Tensor | None = None) -> torch.Tensor:
+        """The FourierUnit's transforms on their own (tests): x [B,H,W,C2] fp32 -> spectrum [B,H,W//2+1,C2,2] = rfftn(x, dim=(1,2),
+        norm="ortho"); given `spec`, returns x + irfftn(spec, s=(H,W), dim=(1,2), norm="ortho") instead (spec is overwritten)."""
+        _require_cuda_f32(x, "x")
+        B, H, W, C2 = x.shape
+        x = x.contiguous().clone()
+        if spec is None:
+            out = torch.empty((B, H, W // 2 + 1, C2, 2), device=x.device, dtype=torch.float32)
+            check(self.L.xsd_swinfir_test_fft(self.h, x.data_ptr(), out.data_ptr(), B, H, W, C2, 0, _stream_ptr(x.device)))
+            return out
+        _require_cuda_f32(spec, "spec")
+        spec = spec.contiguous().clone()
+        check(self.L.xsd_swinfir_test_fft(self.h, x.data_ptr(), spec.data_ptr(), B, H, W, C2, 1, _stream_ptr(x.device)))
+        return x
+
+
+def fft_size_supported(n: int) -> bool:
+    """csrc/swinfir.hip: the FourierUnit's FFT takes lengths up to 4096 whose prime factors are all <= 13"""
+    return bool(_lib.load().xsd_swinfir_fft_supported(int(n)))
+
+
 # ---- stateless transform entry points --------------------------------------------------------------------------
 @_on_tensor_device
 def mask_pad_normalize(counts: torch.Tensor, mask: torch.Tensor | None, res: int, max_val: float | None,

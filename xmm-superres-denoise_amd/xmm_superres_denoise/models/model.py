@@ -1,5 +1,5 @@
 """`Model`: the reference's LightningModule (models/model.py:13-247) restated without Lightning for the RRDB paths and the
-Restormer forward:
+Restormer and SwinFIR forwards:
 constructor signature, `configure_model` factory (model.py:153-186), `forward` = clamp(generator(x), 0, 1)
 (model.py:48-49 -- the second clamp is fused in the engine's output kernel and is idempotent), `_on_step` / `_on_epoch_end` (model.py:72-150, returning what the reference logs) and `configure_optimizers`
 (model.py:239-247).
@@ -49,8 +49,8 @@ class Model(nn.Module):
     def forward(self, x) -> torch.Tensor:
         if self.model is None:
             self.configure_model()
-        if BaseModels(self.config.name) is BaseModels.RESTORMER:
-            # the reference clamps here (model.py:48-49); Restormer itself does not (restormer.py:404)
+        if BaseModels(self.config.name) in (BaseModels.RESTORMER, BaseModels.SWINFIR):
+            # the reference clamps here (model.py:48-49); Restormer and SwinFIR themselves do not (restormer.py:404, swinfir.py:441)
             return torch.clamp(self.model(x), min=0.0, max=1.0)
         # the generator already returns clamp(clamp(.)) == clamp(.)
         return self.model(x)
@@ -58,7 +58,7 @@ class Model(nn.Module):
     def configure_model(self) -> None:
         if self.model is not None:
             return
-        from xmm_superres_denoise.models import GeneratorRRDB_DN, GeneratorRRDB_SR, Restormer
+        from xmm_superres_denoise.models import GeneratorRRDB_DN, GeneratorRRDB_SR, Restormer, SwinFIR
         name = BaseModels(self.config.name)
         if name is BaseModels.ESR_GEN:
             up_scale = self.hr_shape[0] / self.lr_shape[0]
@@ -81,9 +81,19 @@ class Model(nn.Module):
             # reference model.py:226-234: only the channel counts and dim come from the config; forward only on this engine
             self.model = Restormer(inp_channels=self.config.model.in_channels, out_channels=self.config.model.out_channels,
                                    dim=self.config.model.dim)
+        elif name is BaseModels.SWINFIR:
+            # reference model.py:187-200: everything else is SwinFIR's default (upscale 2, SFB, mlp_ratio 4, ...)
+            m = self.config.model
+            self.model = SwinFIR(img_size=m.img_size, window_size=m.window_size, patch_size=m.patch_size, embed_dim=m.embed_dim,
+                                 num_heads=m.num_heads, depths=m.depths, upsampler=m.upsampler, in_chans=m.in_channels,
+                                 use_checkpoint=self.config.memory_efficient)
+        elif name is BaseModels.DRCT:
+            raise NotImplementedError("drct: DRCT is not on the MI355X engine: in the reference its transformer body is dead code (every "
+                                      "RDG returns its input unchanged, drct.py RDG.forward), so a drop-in would be a few convs (SURVEY.md "
+                                      "section 8)")
         else:
-            raise NotImplementedError(f"{name}: only the RRDB generators and Restormer are on the MI355X engine (SURVEY.md section 8; "
-                                      "SwinFIR, DRCT and HAT need timm)")
+            raise NotImplementedError(f"{name}: HAT is not on the MI355X engine (it needs overlapping cross-attention and channel "
+                                      "attention on top of SwinFIR's Swin kernels; SURVEY.md section 8)")
 
     def training_step(self, batch, batch_idx=0):
         return self._on_step(batch, "train")

@@ -64,6 +64,9 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
     if name == "restormer":
         raise NotImplementedError("restormer: training Restormer is not on the MI355X engine (forward only: inference, infer.py, "
                                   "validation / test metrics); fit supports rrdb_denoise and esr_gen")
+    if name == "swinfir":
+        raise NotImplementedError("swinfir: training SwinFIR is not on the MI355X engine (forward only: inference, infer.py, "
+                                  "validation / test metrics); fit supports rrdb_denoise and esr_gen")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -133,8 +136,8 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
 def main():
     ap = argparse.ArgumentParser(description="fit an RRDB generator on synthetic tiles with the MI355X engine")
     ap.add_argument("routine", choices=["fit"])
-    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer"],
-                    help="restormer is refused: forward only on this engine")
+    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer", "swinfir"],
+                    help="restormer and swinfir are refused: forward only on this engine")
     ap.add_argument("--lr-res", type=int, default=416)
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
