@@ -171,6 +171,19 @@ int xsd_mask_pad_normalize(const void* dev_counts, int counts_is_int32, const ui
 int xsd_compose_input(const void* dev_img, const void* dev_agn_or_null, const void* dev_bkg_or_null, int is_int32, int big_endian,
                       const uint8_t* dev_mask_or_null, float* dev_out, int B, int Hin, int Win, int upsample, int res,
                       int do_normalize, float max_val, int stretch, void* stream);
+/* Batched xsd_compose_input from a device pool of FITS data blocks (XmmDataset.load_sample + __getitem__, data/dataset.py:24-49,
+ * :237-268; transforms/normalize.py:66-82; transforms/imageupsample.py:10-26; data/tools.py:103-126).  dev_pool holds n_slots
+ * equal slots of slot_elems words (>= Hin x Win), each one file's primary-HDU data block: BITPIX 32 (is_int32) or -32 words, in
+ * FITS byte order when big_endian != 0.  Sample b: out[b] = normalize(pad(upsample(mask * ((pool[img_idx[b]] + pool[agn_idx[b]])
+ * + pool[bkg_idx[b]])))), the arithmetic of xsd_compose_input, so the two are bitwise equal.  The index arrays are HOST arrays of
+ * B int32 (-1 in agn / bkg = absent for that sample; a NULL array = absent for all): they are checked here before anything is
+ * launched (an index outside [0, n_slots) is XSD_ERR_ARG naming the sample) and travel in the kernel's argument block, so a
+ * batch needs no device index buffer.  One launch per 128 samples; no cross-sample work, so a sample's bits do not depend on
+ * its batch. */
+int xsd_compose_batch(const void* dev_pool, int is_int32, int big_endian, int64_t slot_elems, int64_t n_slots,
+                      const int32_t* img_idx, const int32_t* agn_idx_or_null, const int32_t* bkg_idx_or_null,
+                      const uint8_t* dev_mask_or_null, float* dev_out, int B, int Hin, int Win, int upsample, int res,
+                      int do_normalize, float max_val, int stretch, void* stream);
 /* Normalize.normalize_image (inverse = 0) / denormalize_image (inverse = 1), max_val > 0 (transforms/normalize.py:66-92) */
 int xsd_normalize(const float* dev_in, float* dev_out, int64_t n, float max_val, int stretch, int inverse, void* stream);
 /* ImageUpsample: nearest x scale then / scale^2 (transforms/imageupsample.py:10-26); in [N][H][W] */

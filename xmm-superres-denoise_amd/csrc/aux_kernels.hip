@@ -527,6 +527,47 @@ __global__ void mask_pad_normalize_kernel(MaskPadParams P)
     }
 }
 
+// Batched gather-compose from a pool of FITS data blocks (include/xsd.h: xsd_compose_batch).  blockIdx.y = sample, so the
+// sample's slot numbers are wave-uniform reads of the argument block.  Per output pixel the arithmetic is exactly
+// mask_pad_normalize_kernel's: img (+ agn) (+ bkg) in fp32, * mask, / s^2, normalize -- the two are bitwise equal.
+__device__ __forceinline__ float cb_load(const ComposeBatchParams& P, const unsigned int* slot, long long idx)
+{
+    unsigned int w = slot[idx];
+    if (P.big_endian) w = __builtin_bswap32(w);
+    return P.is_int32 ? (float)(int)w : __builtin_bit_cast(float, w);
+}
+__global__ void compose_batch_kernel(ComposeBatchParams P)
+{
+    const int b = blockIdx.y;
+    const int s = P.upsample;
+    const int Hs = P.Hin * s, Ws = P.Win * s;
+    const long long plane = (long long)P.res * P.res;
+    const unsigned int* img = P.pool + (long long)P.img[b] * P.slot_elems;
+    const unsigned int* agn = P.agn[b] >= 0 ? P.pool + (long long)P.agn[b] * P.slot_elems : nullptr;
+    const unsigned int* bkg = P.bkg[b] >= 0 ? P.pool + (long long)P.bkg[b] * P.slot_elems : nullptr;
+    float* out = P.out + (long long)b * plane;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (long long)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % P.res), oy = (int)(i / P.res);
+        const int uy = oy - P.y_top, ux = ox - P.x_left;
+        float v = 0.f;
+        if (uy >= 0 && uy < Hs && ux >= 0 && ux < Ws) {
+            const int iy = uy / s, ix = ux / s;
+            const long long src = (long long)iy * P.Win + ix;
+            v = cb_load(P, img, src);
+            if (agn) v += cb_load(P, agn, src);
+            if (bkg) v += cb_load(P, bkg, src);
+            if (P.mask) v = v * (float)P.mask[src];
+            if (s > 1) v = v / (float)(s * s);
+        }
+        if (P.do_norm) {
+            v = clamp_nan(v, 0.f, P.max_val) / P.max_val;
+            v = stretch_fwd(v, P.mode);
+            v = clamp_nan(v, 0.f, 1.f);
+        }
+        out[i] = v;
+    }
+}
+
 // Normalize.normalize_image with max_val > 0 / denormalize_image (normalize.py:66-92), elementwise.
 __global__ void normalize_kernel(const float* in, float* out, long long n, float max_val, int mode, int inverse)
 {
@@ -695,6 +736,14 @@ hipError_t launch_mask_pad_normalize(const MaskPadParams& p, hipStream_t s)
 {
     const long long total = (long long)p.B * p.res * p.res;
     hipLaunchKernelGGL(mask_pad_normalize_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_compose_batch(const ComposeBatchParams& p, hipStream_t s)
+{
+    // x covers one sample's res^2 plane (grid-stride), y the samples: the grid is sized by B x res^2
+    const long long plane = (long long)p.res * p.res;
+    const int gx = (int)std::min<long long>((plane + 255) / 256, 1024);
+    hipLaunchKernelGGL(compose_batch_kernel, dim3(gx, p.B), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 hipError_t launch_normalize(const float* in, float* out, long long n, float max_val, int mode, int inverse, hipStream_t s)

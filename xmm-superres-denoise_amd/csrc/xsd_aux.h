@@ -21,6 +21,25 @@ struct MaskPadParams {
     int upsample;              // nearest x s then / s^2 before the pad (ImageUpsample, dataset.py:44-45); 1 = none
 };
 
+// xsd_compose_batch: per-sample pool slots travel in the kernel argument block (no device index buffer, no readback);
+// a launch covers at most COMPOSE_BATCH_CHUNK samples, the entry point splits larger batches
+constexpr int COMPOSE_BATCH_CHUNK = 128;
+struct ComposeBatchParams {
+    const unsigned int* pool;  // [n_slots][slot_elems] words (int32 or float32, optionally FITS big-endian)
+    const uint8_t* mask;       // [Hin][Win] or null
+    float* out;                // [B][res][res] of this chunk
+    long long slot_elems;
+    int is_int32, big_endian;
+    int B, Hin, Win, res, upsample;
+    int y_top, x_left;
+    int do_norm, mode;
+    float max_val;
+    int32_t img[COMPOSE_BATCH_CHUNK];  // slot of sample b's image
+    int32_t agn[COMPOSE_BATCH_CHUNK];  // -1 = absent
+    int32_t bkg[COMPOSE_BATCH_CHUNK];  // -1 = absent
+};
+hipError_t launch_compose_batch(const ComposeBatchParams& p, hipStream_t s);
+
 hipError_t launch_conv3x3_mfma(const ConvParams& p, hipStream_t stream);
 hipError_t launch_wgrad_mfma(const WgradParams& p, hipStream_t stream);
 hipError_t launch_wgrad_reduce(const WgradReduceParams& r, hipStream_t stream);

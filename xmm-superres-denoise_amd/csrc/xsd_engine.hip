@@ -1585,6 +1585,44 @@ int xsd_compose_input(const void* dev_img, const void* dev_agn_or_null, const vo
     return XSD_OK;
 }
 
+int xsd_compose_batch(const void* dev_pool, int is_int32, int big_endian, int64_t slot_elems, int64_t n_slots,
+                      const int32_t* img_idx, const int32_t* agn_idx_or_null, const int32_t* bkg_idx_or_null,
+                      const uint8_t* dev_mask_or_null, float* dev_out, int B, int Hin, int Win, int upsample, int res,
+                      int do_normalize, float max_val, int stretch, void* stream)
+{
+    if (!dev_pool || !img_idx || !dev_out || B < 1 || Hin < 1 || Win < 1 || res < 1 || upsample < 1 || n_slots < 1)
+        return fail(XSD_ERR_ARG, "xsd_compose_batch: bad argument");
+    if (slot_elems < (int64_t)Hin * Win) return fail(XSD_ERR_ARG, "xsd_compose_batch: slot of %lld words < Hin x Win = %d x %d", (long long)slot_elems, Hin, Win);
+    if (stretch < 0 || stretch > 3) return fail(XSD_ERR_ARG, "stretch must be 0..3");
+    if (do_normalize && !(max_val > 0.f)) return fail(XSD_ERR_ARG, "max_val must be > 0 on the fused path");
+    // every index is checked here, before anything is launched: a bad one is an error that names the sample, never a device fault
+    for (int b = 0; b < B; ++b) {
+        if (img_idx[b] < 0 || img_idx[b] >= n_slots)
+            return fail(XSD_ERR_ARG, "xsd_compose_batch: sample %d: img slot %d outside the pool's %lld slots", b, img_idx[b], (long long)n_slots);
+        if (agn_idx_or_null && (agn_idx_or_null[b] < -1 || agn_idx_or_null[b] >= n_slots))
+            return fail(XSD_ERR_ARG, "xsd_compose_batch: sample %d: agn slot %d outside the pool's %lld slots (-1 = absent)", b, agn_idx_or_null[b], (long long)n_slots);
+        if (bkg_idx_or_null && (bkg_idx_or_null[b] < -1 || bkg_idx_or_null[b] >= n_slots))
+            return fail(XSD_ERR_ARG, "xsd_compose_batch: sample %d: bkg slot %d outside the pool's %lld slots (-1 = absent)", b, bkg_idx_or_null[b], (long long)n_slots);
+    }
+    ComposeBatchParams p; memset(&p, 0, sizeof(p));
+    p.pool = (const unsigned int*)dev_pool; p.mask = dev_mask_or_null; p.slot_elems = slot_elems;
+    p.is_int32 = is_int32 != 0; p.big_endian = big_endian != 0;
+    p.Hin = Hin; p.Win = Win; p.res = res; p.upsample = upsample;
+    p.y_top = (int)std::floor((res - Hin * upsample) / 2.0); p.x_left = (int)std::floor((res - Win * upsample) / 2.0);
+    p.do_norm = do_normalize; p.mode = stretch; p.max_val = max_val;
+    for (int b0 = 0; b0 < B; b0 += COMPOSE_BATCH_CHUNK) {
+        p.B = std::min(COMPOSE_BATCH_CHUNK, B - b0);
+        p.out = dev_out + (int64_t)b0 * res * res;
+        for (int b = 0; b < p.B; ++b) {
+            p.img[b] = img_idx[b0 + b];
+            p.agn[b] = agn_idx_or_null ? agn_idx_or_null[b0 + b] : -1;
+            p.bkg[b] = bkg_idx_or_null ? bkg_idx_or_null[b0 + b] : -1;
+        }
+        HIPCHK(launch_compose_batch(p, (hipStream_t)stream));
+    }
+    return XSD_OK;
+}
+
 int xsd_normalize(const float* dev_in, float* dev_out, int64_t n, float max_val, int stretch, int inverse, void* stream)
 {
     if (!dev_in || !dev_out || n <= 0 || !(max_val > 0.f) || stretch < 0 || stretch > 3) return fail(XSD_ERR_ARG, "bad argument");

@@ -1,9 +1,10 @@
 """The slice of the reference's pydantic config that defines the constructor-API contract of the hot path
 (reference config/config.py:36-42,164-203).  Python 3.10 here: enum.StrEnum restated as (str, Enum)."""
 from enum import Enum
-from typing import List, Literal, Tuple, Union
+from pathlib import Path
+from typing import List, Literal, Optional, Tuple, Union
 
-from pydantic import BaseModel, Field, NonNegativeFloat, PositiveInt, model_validator
+from pydantic import BaseModel, Field, NonNegativeFloat, NonNegativeInt, PositiveInt, model_validator
 
 
 class BaseModels(str, Enum):
@@ -111,3 +112,83 @@ class LossCfg(BaseModel):
         if 0 < p_sum <= 1:
             return self
         raise ConfigError(f"Sum of relative percentages has to be between 0 and 1, got {p_sum}!")
+
+
+# ---- dataset section (reference config/config.py:24-33,77-161) ----------------------------------------------------------
+class DatasetType(str, Enum):
+    SIM = "sim"
+    REAL = "real"
+    BORING = "boring"
+
+    def __str__(self):
+        return self.value
+
+
+class ImageType(str, Enum):
+    IMG = "img"
+    AGN = "agn"
+    BKG = "bkg"
+
+    def __str__(self):
+        return self.value
+
+
+class HrDatasetCfg(BaseModel):
+    det_mask: Optional[Path] = None
+    agn: bool = True
+    exp: NonNegativeInt = 100
+    clamp_max: NonNegativeFloat = 0.0005584
+    res: PositiveInt = 832
+
+
+class LrDatasetCfg(BaseModel):
+    bkg: Union[bool, NonNegativeInt] = 1
+    det_mask: Optional[Path] = None
+    exps: List[PositiveInt] = [20]
+    clamp_max: NonNegativeFloat = 0.0022336
+    res: PositiveInt = 416
+
+
+class DatasetCfg(BaseModel):
+    """reference config/config.py:102-161 (defaults: res/baseline_config.toml [dataset]).  The file-existence validators of the
+    detector masks run where the masks are read (data/dataset.py)."""
+    agn: Union[bool, NonNegativeInt] = 1
+    batch_size: PositiveInt = 1
+    check_files: bool = False
+    debug: bool = False
+    comb_hr: bool = False
+    crop_mode: Literal["center", "random", "boresight"] = "center"
+    directory: Path
+    mode: Literal["img", "agn"] = "img"
+    name: str = "sim_dataset"
+    scaling: Literal["linear", "sqrt", "asinh", "log"] = "sqrt"
+    type: DatasetType = DatasetType.SIM
+    lr: LrDatasetCfg = LrDatasetCfg()
+    hr: Optional[HrDatasetCfg] = HrDatasetCfg()
+
+    @property
+    def res_mult(self) -> int:
+        if self.type is DatasetType.REAL:
+            return 1
+        return self.hr.res // self.lr.res
+
+    @property
+    def img_dir(self) -> Path:
+        return self._mode_dir(ImageType.IMG)
+
+    @property
+    def agn_dir(self) -> Path:
+        return self._mode_dir(ImageType.AGN)
+
+    @property
+    def bkg_dir(self) -> Path:
+        return self._mode_dir(ImageType.BKG)
+
+    def _mode_dir(self, mode: ImageType) -> Path:
+        # <directory>/<name>/{img,agn,bkg} for simulations; real data has images only, at <directory>/<name>
+        if self.type is DatasetType.SIM:
+            return Path(self.directory) / self.name / mode.value
+        if mode is ImageType.IMG and self.type is DatasetType.REAL:
+            return Path(self.directory) / self.name
+        raise ConfigError(f"Something went wrong while setting {mode.value.upper()} directory for type '{self.type}': "
+                          f"\tPath to {mode.value.upper()} dir has not been set!")

@@ -375,6 +375,32 @@ def compose_input(img: torch.Tensor, agn: torch.Tensor | None, bkg: torch.Tensor
 
 
 @_on_tensor_device
+def compose_batch(pool: torch.Tensor, img_idx, agn_idx, bkg_idx, mask: torch.Tensor | None, Hin: int, Win: int, res: int,
+                  max_val: float | None, stretch: str = "linear", upsample: int = 1, is_int32: bool = True,
+                  big_endian: bool = True) -> torch.Tensor:
+    """Batched gather-compose (include/xsd.h: xsd_compose_batch): pool [n_slots, slot_elems] int32 (CUDA) of raw FITS data
+    blocks; img_idx / agn_idx / bkg_idx: host int32 sequences of B slot numbers (agn / bkg: -1 = absent, None = absent for all).
+    Returns [B,1,res,res] float32, bitwise equal to compose_input on the same slots stacked by hand."""
+    import numpy as np
+    L = _lib.load()
+    if not pool.is_cuda or pool.dtype != torch.int32 or pool.dim() != 2 or not pool.is_contiguous():
+        raise XsdError("pool must be a contiguous CUDA int32 tensor [n_slots, slot_elems]")
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_cuda or tuple(mask.shape) != (Hin, Win)):
+        raise XsdError("mask must be a CUDA uint8 tensor [Hin,Win]")
+    idx = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.int32)) for a in (img_idx, agn_idx, bkg_idx)]
+    B = int(idx[0].size)
+    for n, a in zip(("agn", "bkg"), idx[1:]):
+        if a is not None and a.size != B:
+            raise XsdError(f"{n}_idx holds {a.size} entries for {B} samples")
+    out = torch.empty((B, 1, res, res), device=pool.device, dtype=torch.float32)
+    ptr = [None if a is None else a.ctypes.data for a in idx]
+    check(L.xsd_compose_batch(pool.data_ptr(), int(is_int32), int(big_endian), pool.shape[1], pool.shape[0], ptr[0], ptr[1], ptr[2],
+                              mask.data_ptr() if mask is not None else None, out.data_ptr(), B, Hin, Win, int(upsample), res,
+                              int(max_val is not None), float(max_val or 0.0), STRETCH[stretch], _stream_ptr(pool.device)))
+    return out
+
+
+@_on_tensor_device
 def normalize(img: torch.Tensor, max_val: float, stretch: str, inverse: bool = False) -> torch.Tensor:
     L = _lib.load()
     _require_cuda_f32(img, "img")

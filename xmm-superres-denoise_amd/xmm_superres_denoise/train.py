@@ -2,9 +2,11 @@
 models, without Lightning.  One process per GPU (launch with torch.distributed.run for N > 1); data parallelism and the
 optimizer are `parallel.DataParallelTrainer` (flat-buffer RCCL all-reduce overlapped with backward + fused Adam).
 
-The data feed here is the reference's `BoringDataset` analogue (random tensors of the configured shapes,
-data/dataset.py:52-74): file discovery / FITS matching (`XmmDataset.__init__`) is host I/O outside the hot path; real
-samples are composed on the GPU with `engine.compose_input` (img + agn + background, mask, pad, normalize).
+Without a dataset the feed is the reference's `BoringDataset` analogue (random tensors of the configured shapes,
+data/dataset.py:52-74).  With `dataset_dir` it is the reference's XmmDataset (data/dataset.py): every file is inflated once
+into a device pool of raw FITS words, and each batch is one `xsd_compose_batch` launch per resolution (img + agn +
+background, mask, upsample, pad, normalize); `fit` then validates every epoch, keeps the best val/loss checkpoint and tests it,
+and `test` evaluates a checkpoint on the test split.
 
 Checkpoints use the reference's Lightning layout: {"state_dict": {"model.<key>": tensor}} with the reference key names,
 so `Model.load_from_checkpoint`-style consumers (utils/run_inference_on_file.py:28-35) can read them.
@@ -58,9 +60,19 @@ def load_checkpoint(path: str, model: Model, trainer: DataParallelTrainer | None
 
 def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, steps: int = 10, device: str | None = None,
         checkpoint: str | None = None, seed: int = 0, math: str | None = None, log_every: int = 1,
-        loss: str = "l1", scaling: str = "linear", val_batches: int = 0):
+        loss: str = "l1", scaling: str = "linear", val_batches: int = 0, dataset_dir: str | None = None,
+        dataset_name: str = "sim_dataset", dataset_type: str = "sim", lr_exps=(20,), hr_exp: int = 100, epochs: int = 1,
+        lr_det_mask: str | None = None, hr_det_mask: str | None = None, agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False,
+        splits: str | None = None, max_pool_bytes: int | None = None):
     """loss: "l1" (BASELINE configs[2]) or "paper" = the reference's shipped default, 0.5 psnr + 0.5 ms_ssim with the
-    scaling table of the dataset's stretch mode (`scaling`; res/configs/loss_functions.toml, train.py:46-63)."""
+    scaling table of the dataset's stretch mode (`scaling`; res/configs/loss_functions.toml, train.py:46-63).
+
+    Without `dataset_dir`: random tiles for `steps` steps (the reference's BoringDataset analogue).  With it: the reference's
+    `fit` on an XMM FITS tree (`<dataset_dir>/<dataset_name>/{img,agn,bkg}/<exp>ks/**/<mult>x/`, or real data): `epochs`
+    epochs of shuffled train shards, each followed by a validation epoch (loss + get_metrics + get_in_metrics over the
+    `linear` normaliser, train.py:72-88); the checkpoint of the lowest val/loss is kept (ModelCheckpoint(monitor="val/loss",
+    mode="min")), then a test epoch runs on it.  `scaling` is then the dataset's stretch; lr_res is the dataset's lr.res.
+    The split JSON goes to `splits` (default: next to the checkpoint)."""
     if name == "restormer":
         raise NotImplementedError("restormer: training Restormer is not on the MI355X engine (forward only: inference, infer.py, "
                                   "validation / test metrics); fit supports rrdb_denoise and esr_gen")
@@ -88,6 +100,11 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
+    if dataset_dir is not None:
+        return _fit_dataset(name, batch_size, dev, rank, world, checkpoint, seed, math, log_every, loss, scaling,
+                            dataset_cfg(dataset_dir, dataset_name, dataset_type, name, lr_res, lr_exps, hr_exp, lr_det_mask,
+                                        hr_det_mask, agn, lr_bkg, comb_hr, scaling, batch_size),
+                            epochs, splits, max_pool_bytes)
     cfg = model_cfg(name, batch_size=batch_size)
     hr_res = lr_res * (2 if name == "esr_gen" else 1)
     torch.manual_seed(seed)
@@ -133,9 +150,145 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
     return model, trainer, losses
 
 
+def dataset_cfg(dataset_dir, dataset_name="sim_dataset", dataset_type="sim", name="rrdb_denoise", lr_res=416, lr_exps=(20,),
+                hr_exp=100, lr_det_mask=None, hr_det_mask=None, agn=1, lr_bkg=1, comb_hr=False, scaling="sqrt", batch_size=1):
+    """the [dataset] section of the reference's run config (res/baseline_config.toml) for `name`: HR at lr_res for the
+    denoiser, 2 x lr_res for esr_gen / swinfir; clamp_max values of the baseline config"""
+    from xmm_superres_denoise.config.config import DatasetCfg, HrDatasetCfg, LrDatasetCfg
+    hr_res = lr_res * (2 if name in ("esr_gen", "swinfir") else 1)
+    return DatasetCfg(directory=dataset_dir, name=dataset_name, type=dataset_type, agn=agn, comb_hr=comb_hr, scaling=scaling,
+                      batch_size=batch_size,
+                      lr=LrDatasetCfg(bkg=lr_bkg, det_mask=lr_det_mask, exps=list(lr_exps), res=lr_res),
+                      hr=HrDatasetCfg(det_mask=hr_det_mask, exp=hr_exp, res=hr_res))
+
+
+def _metric_sets(dcfg, stage: str):
+    """get_metrics / get_in_metrics of the reference's train.py:68-88: the dataset normaliser and the `linear` scaling one"""
+    from xmm_superres_denoise.metrics import get_in_metrics, get_metrics
+    from xmm_superres_denoise.transforms import Normalize
+    norm = Normalize(lr_max=dcfg.lr.clamp_max, hr_max=dcfg.hr.clamp_max, stretch_mode=dcfg.scaling)
+    lin = [Normalize(lr_max=dcfg.lr.clamp_max, hr_max=dcfg.hr.clamp_max, stretch_mode="linear")]
+    return get_metrics(norm, lin, stage), get_in_metrics(norm, lin, stage)
+
+
+EXT_METRICS_NOTICE = ("test: the extended metric collection (get_ext_metrics / get_in_ext_metrics: piq and VIF) is not on the "
+                      "MI355X engine and is not computed; reported: loss, get_metrics and get_in_metrics")
+
+
+def _eval_epoch(model: Model, dm, stage: str, per_rank: int, epoch: int) -> dict:
+    """one validation / test epoch over this rank's shard (reference model.py:53-66 + _on_epoch_end); states are reduced over
+    the ranks, so every rank returns the global values"""
+    if stage == "val":
+        model.on_validation_start()
+    for idx in dm.batches(stage, per_rank, epoch):
+        batch = dm.dataset.batch(idx, epoch)
+        model.validation_step(batch) if stage == "val" else model.test_step(batch)
+    return model.on_validation_epoch_end() if stage == "val" else model.on_test_epoch_end()
+
+
+def _print_logged(title: str, logged: dict) -> None:
+    print(f"{title}: " + ", ".join(f"{k} {float(v):.6f}" for k, v in sorted(logged.items())), flush=True)
+
+
+def _fit_dataset(name, batch_size, dev, rank, world, checkpoint, seed, math, log_every, loss, scaling, dcfg, epochs, splits,
+                 max_pool_bytes):
+    from xmm_superres_denoise.data.datamodule import XmmDataModule
+    from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
+    cfg = model_cfg(name, batch_size=batch_size)
+    torch.manual_seed(seed)
+    splits = splits or os.path.join(os.path.dirname(os.path.abspath(checkpoint)) if checkpoint else os.getcwd(),
+                                    f"{dcfg.name}_{dcfg.type}_{dcfg.mode}_splits.json")
+    if rank == 0:       # the first run writes the split file; the other ranks read it
+        XmmDataModule(dcfg, splits, seed=seed).prepare_data()
+    if dist.is_initialized():
+        dist.barrier()
+    dm = XmmDataModule(dcfg, splits, seed=seed, rank=rank, world=world).setup("fit", device=dev, max_pool_bytes=max_pool_bytes)
+    loss_fn = create_loss(*load_loss_config(scaling)) if loss != "l1" else None
+    metrics, in_metrics = _metric_sets(dcfg, "val")
+    model = Model(cfg, (dcfg.lr.res, dcfg.lr.res), (dcfg.hr.res, dcfg.hr.res),
+                  loss=loss_fn if loss_fn is not None else Loss({"l1": 1.0}), metrics=metrics, extended_metrics=None,
+                  in_metrics=in_metrics, in_extended_metrics=None)
+    model.configure_model()
+    model.to(dev)
+    if math:
+        model.model.set_math(math)
+    trainer = DataParallelTrainer(model.model, lr=cfg.optimizer.learning_rate, betas=cfg.optimizer.betas, loss=loss_fn)
+    per_rank = batch_size // world if batch_size % world == 0 else batch_size
+    if rank == 0 and log_every:
+        print(f"dataset {dcfg.directory}/{dcfg.name}: {dm.dataset.dataset_size} samples, split "
+              + " / ".join(f"{s} {len(dm.samples[s])}" for s in ("train", "val", "test"))
+              + f", pool {dm.dataset.pool_bytes / 2**20:.1f} MiB, splits {splits}", flush=True)
+    losses, history, best, best_state = [], [], None, None
+    for epoch in range(epochs):
+        ep = []
+        for idx in dm.batches("train", per_rank, epoch):
+            lr_img, hr_img = dm.dataset.batch(idx, epoch)
+            ep.append(float(trainer.global_loss(trainer.train_step(lr_img, hr_img))))
+        losses.extend(ep)
+        logged = _eval_epoch(model, dm, "val", per_rank, epoch)
+        vl = float(logged["val/loss"])
+        history.append({"epoch": epoch, "train/loss": sum(ep) / max(1, len(ep)), "val/loss": vl})
+        if rank == 0 and log_every:
+            print(f"epoch {epoch}: train/loss {history[-1]['train/loss']:.6f} val/loss {vl:.6f}", flush=True)
+        if best is None or vl < best:       # ModelCheckpoint(monitor="val/loss", mode="min")
+            best = vl
+            best_state = {k: v.detach().clone() for k, v in model.model.state_dict().items()}
+            if checkpoint and rank == 0:
+                save_checkpoint(checkpoint, model, trainer, epoch=epoch)
+    # trainer.test(ckpt_path="best"): the test epoch on the best weights, with the test-prefixed metric sets
+    model.model.load_state_dict(best_state)
+    model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
+    test_logged = _eval_epoch(model, dm, "test", per_rank, 0)
+    if rank == 0 and log_every:
+        _print_logged(f"test (best val/loss {best:.6f})", test_logged)
+        print(EXT_METRICS_NOTICE, flush=True)
+    model.history, model.test_logged = history, test_logged
+    return model, trainer, losses
+
+
+def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_name: str = "sim_dataset",
+         dataset_type: str = "sim", lr_res: int = 416, lr_exps=(20,), hr_exp: int = 100, lr_det_mask=None, hr_det_mask=None,
+         agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False, scaling: str = "linear", batch_size: int = 4, loss: str = "l1",
+         seed: int | None = None, splits: str | None = None, device: str | None = None, max_pool_bytes: int | None = None,
+         log: bool = True) -> dict:
+    """The reference's `train.py test` (train.py:91-103,165-171) on one device: the test split of the dataset through the model
+    of `checkpoint` (any model infer.load_model loads), returning the `test/...` values (loss, get_metrics, get_in_metrics).
+    The split file must be the one `fit` wrote (default location: next to the checkpoint); `seed` defaults to the one recorded
+    there, so the test samples draw the same realisations, AGN and backgrounds as fit's test epoch.  The extended piq / VIF collection
+    is not on the engine: the routine says so (EXT_METRICS_NOTICE) instead of leaving it out silently."""
+    from xmm_superres_denoise.data.datamodule import XmmDataModule
+    from xmm_superres_denoise.infer import load_model
+    from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
+    if torch.cuda.device_count() < 1:
+        raise RuntimeError("train.py needs an MI355X (no HIP device visible); there is no CPU fallback")
+    dev = torch.device(device or "cuda:0")
+    torch.cuda.set_device(dev)
+    dcfg = dataset_cfg(dataset_dir, dataset_name, dataset_type, name, lr_res, lr_exps, hr_exp, lr_det_mask, hr_det_mask, agn,
+                       lr_bkg, comb_hr, scaling, batch_size)
+    splits = splits or os.path.join(os.path.dirname(os.path.abspath(checkpoint)), f"{dcfg.name}_{dcfg.type}_{dcfg.mode}_splits.json")
+    if not os.path.exists(splits):
+        raise FileNotFoundError(f"{splits}: no split file (fit writes it next to its checkpoint; pass splits= to name another)")
+    if seed is None:
+        import json
+        with open(splits) as f:
+            seed = int(json.load(f).get("seed", 0))
+    dm = XmmDataModule(dcfg, splits, seed=seed).setup("test", device=dev, max_pool_bytes=max_pool_bytes)
+    model = load_model(checkpoint, name, lr_res, device=dev)
+    model.loss = create_loss(*load_loss_config(scaling)) if loss != "l1" else Loss({"l1": 1.0})
+    model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
+    with torch.no_grad():
+        logged = _eval_epoch(model, dm, "test", batch_size, 0)
+    logged = {k: float(v) for k, v in logged.items()}
+    if log:
+        _print_logged("test", logged)
+        print(EXT_METRICS_NOTICE, flush=True)
+    return logged
+
+
 def main():
-    ap = argparse.ArgumentParser(description="fit an RRDB generator on synthetic tiles with the MI355X engine")
-    ap.add_argument("routine", choices=["fit"])
+    ap = argparse.ArgumentParser(description="fit an RRDB generator with the MI355X engine, on random tiles or an XMM FITS dataset; "
+                                             "test a checkpoint on a dataset's test split")
+    ap.add_argument("routine", choices=["fit", "test"])
     ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer", "swinfir"],
                     help="restormer and swinfir are refused: forward only on this engine")
     ap.add_argument("--lr-res", type=int, default=416)
@@ -146,8 +299,32 @@ def main():
     ap.add_argument("--loss", default="l1", choices=["l1", "paper"], help="paper = 0.5 psnr + 0.5 ms_ssim (loss_functions.toml)")
     ap.add_argument("--scaling", default="linear", choices=["linear", "sqrt", "asinh", "log"])
     ap.add_argument("--val-batches", type=int, default=0, help="validation batches after training (loss + metric set)")
+    ap.add_argument("--dataset-dir", default=None, help="train / test on the FITS tree <dir>/<dataset-name>/... (default: random tiles)")
+    ap.add_argument("--dataset-name", default="sim_dataset")
+    ap.add_argument("--dataset-type", default="sim", choices=["sim", "real"])
+    ap.add_argument("--lr-exps", type=int, nargs="+", default=[20])
+    ap.add_argument("--hr-exp", type=int, default=100)
+    ap.add_argument("--epochs", type=int, default=1)
+    ap.add_argument("--lr-det-mask", default=None)
+    ap.add_argument("--hr-det-mask", default=None)
+    ap.add_argument("--agn", type=int, default=1)
+    ap.add_argument("--lr-bkg", type=int, default=1)
+    ap.add_argument("--comb-hr", action="store_true")
+    ap.add_argument("--splits", default=None, help="split JSON (default: next to the checkpoint)")
+    ap.add_argument("--seed", type=int, default=None, help="fit: default 0; test: default the seed recorded in the split file")
     a = ap.parse_args()
-    fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling, val_batches=a.val_batches)
+    ds = dict(dataset_name=a.dataset_name, dataset_type=a.dataset_type, lr_exps=tuple(a.lr_exps), hr_exp=a.hr_exp,
+              lr_det_mask=a.lr_det_mask, hr_det_mask=a.hr_det_mask, agn=a.agn, lr_bkg=a.lr_bkg, comb_hr=a.comb_hr, splits=a.splits)
+    if a.routine == "test":
+        if not a.checkpoint or not a.dataset_dir:
+            ap.error("test needs --checkpoint and --dataset-dir")
+        test(a.checkpoint, a.dataset_dir, name=a.model, lr_res=a.lr_res, scaling=a.scaling, batch_size=a.batch_size, loss=a.loss,
+             seed=a.seed, **ds)
+    elif a.dataset_dir is None:
+        fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling, val_batches=a.val_batches)
+    else:
+        fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling,
+            seed=0 if a.seed is None else a.seed, dataset_dir=a.dataset_dir, epochs=a.epochs, **ds)
     if dist.is_initialized():
         dist.destroy_process_group()
 
