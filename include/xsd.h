@@ -152,6 +152,28 @@ int xsd_loss_eval(xsd_loss_fn* f, const float* dev_y, const float* dev_target, f
  * the same either way.  xsd_loss_eval then requires B to be a multiple of `channels`. */
 int xsd_loss_set_channels(xsd_loss_fn* f, int channels);
 
+/* The reference's extended test metrics (get_ext_metrics / get_in_ext_metrics, metrics/xmm_metric_collection.py:41-61,91-111;
+ * metrics/metrics.py:42-101, every default, chromatic=False) on single-channel images in [0, 1]: piq 0.7.x gmsd, multi_scale_gmsd,
+ * haarpsi (scales=3, subsample=True, c=30, alpha=4.2), mdsi (c1=140, c2=55, c3=550, combination="sum", alpha=0.6, rho=1, q=0.25,
+ * o=0.25; the reference's key spells it "msdi") and torchmetrics 1.x VisualInformationFidelity(sigma_n_sq=2.0).  The formulas are
+ * restated from the libraries' published code (tests/golden/ext_metrics_torch.py holds them in plain torch):
+ * neither library is available to this project, so parity with the libraries themselves is unpinned, as for psnr / ssim / ms_ssim.
+ * fsim is not built (phase congruency needs 2-D FFTs of sizes the engine's FFT does not take, and a per-image median).
+ * preds, target: [B][H][W] fp32; values outside [0, 1] are not checked.  dev_out: B x XSD_EXTM_OUT device DOUBLES, per image
+ *   [0] gmsd   [1] ms_gmsd   [2] haarpsi   [3] mdsi   [4] vif numerator   [5] vif denominator   (vif_p = [4] / [5]; a constant
+ *   target gives 0 / 0 as in torchmetrics).
+ * Per-image values, not batch means: the caller does the reference's reductions (metrics/metrics.py:9-27).  The maps are fp32, every
+ * sum over an image is carried in double in a fixed order: an image's six values are bitwise independent of its batch-mates and of
+ * the run, and a NaN / inf pixel stays in its image.  A fixed number of launches (11) whatever B is.  The object owns a device
+ * workspace sized at first use per (B, H, W), on the device that is current at that call.
+ * Refused with XSD_ERR_ARG: null pointers, B < 1, H or W < 41 (VIF's 17-tap valid filter over four scales). */
+#define XSD_EXTM_OUT 6
+typedef struct xsd_ext_metrics xsd_ext_metrics;
+int xsd_ext_metrics_create(xsd_ext_metrics** out);
+void xsd_ext_metrics_destroy(xsd_ext_metrics* m);
+int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float* dev_target, double* dev_out, int B, int H, int W,
+                         void* stream);
+
 /* torch.optim.Adam(lr, betas, eps=1e-8) single fused step over flat buffers (models/model.py:241-245).
  * step is 1-based; grad_scale multiplies the gradient on read (1/world_size for data-parallel mean). */
 int xsd_adam_step(xsd_engine* e, float* dev_params, const float* dev_grads, float* dev_m, float* dev_v, int64_t n,

@@ -322,6 +322,47 @@ class SwinFIREngine:
         return x
 
 
+class ExtMetricsEngine:
+    """The extended test metrics of one batch (include/xsd.h: xsd_ext_metrics_eval): gmsd, ms_gmsd, haarpsi, mdsi and the two
+    VIF sums per image, as doubles.  The formulas restate piq 0.7.x / torchmetrics 1.x from their published code; parity with
+    the libraries themselves is unpinned.  One object per GPU; it owns a device workspace."""
+
+    OUT = 6          # XSD_EXTM_OUT: gmsd, ms_gmsd, haarpsi, mdsi, vif numerator, vif denominator
+
+    def __init__(self):
+        self.L = _lib.load()
+        h = ctypes.c_void_p()
+        check(self.L.xsd_ext_metrics_create(ctypes.byref(h)))
+        self.h = h
+        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.xsd_ext_metrics_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @_on_engine_device
+    def eval(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """preds, target: [B, H, W] (or [B, 1, H, W]) fp32 in [0, 1] on this engine's device -> [B, 6] float64 per-image values"""
+        _require_cuda_f32(preds, "preds")
+        _require_cuda_f32(target, "target")
+        if preds.shape != target.shape:
+            raise XsdError(f"shape mismatch {tuple(preds.shape)} vs {tuple(target.shape)}")
+        if preds.dim() == 4 and preds.shape[1] == 1:
+            preds, target = preds[:, 0], target[:, 0]
+        if preds.dim() != 3:
+            raise XsdError(f"expected [B,H,W] or [B,1,H,W], got {tuple(preds.shape)}")
+        if preds.device.index != self.device_index:
+            raise XsdError(f"preds is on cuda:{preds.device.index}, this engine's workspace on cuda:{self.device_index}")
+        B, H, W = preds.shape
+        out = torch.empty((B, self.OUT), device=preds.device, dtype=torch.float64)
+        check(self.L.xsd_ext_metrics_eval(self.h, preds.data_ptr(), target.data_ptr(), out.data_ptr(), B, H, W, _stream_ptr(preds.device)))
+        return out
+
+
 def fft_size_supported(n: int) -> bool:
     """csrc/swinfir.hip: the FourierUnit's FFT takes lengths up to 4096 whose prime factors are all <= 13"""
     return bool(_lib.load().xsd_swinfir_fft_supported(int(n)))

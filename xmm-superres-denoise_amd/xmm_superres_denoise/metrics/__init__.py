@@ -1,1 +1,2 @@
-from .xmm_metric_collection import XMMMetricCollection, get_in_metrics, get_metrics  # noqa: F401
+from .xmm_metric_collection import (EXT_NAMES, ExtEpochState, XMMExtMetricCollection, XMMMetricCollection, get_ext_metrics, get_in_ext_metrics,
+                                    get_in_metrics, get_metrics)  # noqa: F401

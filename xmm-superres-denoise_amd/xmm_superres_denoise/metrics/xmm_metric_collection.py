@@ -11,7 +11,16 @@ torchmetrics classes accumulate theirs, so `compute()` gives epoch-level values,
   l1, l2  sum of absolute / squared errors / n;
   poisson sum of per-batch means / number of images (metrics/metrics.py:30-39 as written).
 `denorm` / `norm` are the bare stretch functions of Normalize (transforms/normalize.py:55-62), applied to [0,1] images as
-in the reference's `update` (:136-143).  The piq / VIF "extended" collections (get_ext_metrics) are third-party arithmetic outside the hot path.
+in the reference's `update` (:136-143).
+
+The "extended" collections of the reference's `test` (get_ext_metrics / get_in_ext_metrics, :41-61,91-111) are XMMExtMetricCollection:
+vif_p, gmsd, ms_gmsd, haarpsi, msdi from one `xsd_ext_metrics_eval` per (batch, stretch mode), which returns per-image doubles; the
+reference's reductions (metrics/metrics.py:9-27) happen here, on the device, in double:
+  gmsd, ms_gmsd, haarpsi, msdi   sum of per-batch MEANS / number of images (the piq wrappers add the batch mean to `metric` and the
+          batch size to `total`: the quirk `poisson` shows too);
+  vif_p   torchmetrics' own class: sum of per-image values / number of images.
+Their formulas restate piq 0.7.x / torchmetrics 1.x from the published code: parity with the libraries is unpinned (INTEGRATION.md
+section 3).  fsim is not built and is refused by name.
 """
 from __future__ import annotations
 
@@ -69,9 +78,110 @@ class XMMMetricCollection:
         return res
 
 
+EXT_NAMES = ("vif_p", "gmsd", "ms_gmsd", "haarpsi", "msdi")
+FSIM_REFUSAL = ("fsim is not on the MI355X engine: its phase congruency needs 2-D FFTs of the pooled image (278 = 2 * 139 points a side "
+                "for 832 x 832 tiles; the engine's FFT takes prime factors up to 13) and a per-image median")
+
+
+class ExtEpochState:
+    """Epoch states of the reference's extended metrics, double, on the device of the values: [gmsd, ms_gmsd, haarpsi, msdi] sums of
+    per-batch means, the sum of per-image vif_p, the number of images."""
+
+    def __init__(self):
+        self.acc = None
+
+    def add(self, per_image: torch.Tensor) -> None:
+        """per_image: [B, 6] float64 of one batch (gmsd, ms_gmsd, haarpsi, mdsi, vif numerator, vif denominator per image)"""
+        v = per_image.double()
+        cur = torch.cat([v[:, :4].mean(0), (v[:, 4] / v[:, 5]).sum().reshape(1), v.new_tensor([float(v.shape[0])])])
+        self.acc = cur if self.acc is None else self.acc + cur
+
+    def sync(self, group=None, device=None) -> None:
+        """sum the states over the ranks (dist_reduce_fx="sum" of every state, metrics/metrics.py:16-21); a rank that saw no batch
+        takes part with zeros, see EpochState.sync"""
+        import torch.distributed as dist
+        from xmm_superres_denoise.parallel import all_reduce_any, collectives_on
+        if not collectives_on(group):
+            return
+        if self.acc is not None:
+            a = self.acc.clone()
+        else:
+            if device is None:
+                device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+            a = torch.zeros(6, dtype=torch.float64, device=device)
+        all_reduce_any(a, dist.ReduceOp.SUM, group)
+        self.acc = None if float(a[5]) == 0.0 else a
+
+    def compute(self) -> dict:
+        a = self.acc
+        return {"gmsd": a[0] / a[5], "ms_gmsd": a[1] / a[5], "haarpsi": a[2] / a[5], "msdi": a[3] / a[5], "vif_p": a[4] / a[5]}
+
+
+class XMMExtMetricCollection:
+    """The reference's XMMMetricCollection over its extended metric set: same constructor, same denorm -> renorm per scaling
+    normaliser, keys "<prefix>/<mode>/<name>"."""
+
+    def __init__(self, metrics, dataset_normalizer, scaling_normalizers: List, prefix: str):
+        self.names = tuple(metrics)
+        for n in self.names:
+            base = n.split("/")[-1]
+            if base == "fsim":
+                raise NotImplementedError(f"metric {n}: {FSIM_REFUSAL}")
+            if base not in EXT_NAMES:
+                raise NotImplementedError(f"metric {n}: the extended set on the MI355X engine is {EXT_NAMES}")
+        self.dataset_normalizer = dataset_normalizer
+        self.normalizer_dict = {n.stretch_mode: n for n in scaling_normalizers}
+        self.prefix = prefix
+        self._engines = {}       # one engine (device workspace) per device
+        self.reset()
+
+    def reset(self):
+        self.states = {mode: ExtEpochState() for mode in self.normalizer_dict}
+
+    def _engine(self, device):
+        from ..engine.engine import ExtMetricsEngine
+        if device.index not in self._engines:
+            with torch.cuda.device(device):
+                self._engines[device.index] = ExtMetricsEngine()
+        return self._engines[device.index]
+
+    @torch.no_grad()
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        if preds.dim() != 4 or preds.shape[1] != 1:
+            raise NotImplementedError(f"extended metrics: only single-channel [B, 1, H, W] images run on the MI355X engine (got "
+                                      f"{tuple(preds.shape)}; piq's RGB / YIQ branches are not built)")
+        preds = self.dataset_normalizer.denorm(preds)
+        target = self.dataset_normalizer.denorm(target)
+        for mode, normalizer in self.normalizer_dict.items():
+            p = normalizer.norm(preds).contiguous()
+            t = normalizer.norm(target).contiguous()
+            self.states[mode].add(self._engine(p.device).eval(p, t))
+
+    def sync(self, group=None) -> None:
+        for st in self.states.values():
+            st.sync(group)
+
+    def compute(self) -> dict:
+        res = {}
+        for mode, st in self.states.items():
+            vals = st.compute()
+            for n in self.names:
+                res[f"{self.prefix}/{mode}/{n}"] = vals[n.rpartition("/")[2]].float()
+        return res
+
+
 def get_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMMetricCollection:
     return XMMMetricCollection(NAMES, dataset_normalizer, scaling_normalizers, prefix)
 
 
 def get_in_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMMetricCollection:
     return XMMMetricCollection(tuple("in/" + n for n in NAMES), dataset_normalizer, scaling_normalizers, prefix)
+
+
+def get_ext_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMExtMetricCollection:
+    """the reference's get_ext_metrics without fsim (refused by name when asked for: XMMExtMetricCollection)"""
+    return XMMExtMetricCollection(EXT_NAMES, dataset_normalizer, scaling_normalizers, prefix)
+
+
+def get_in_ext_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMExtMetricCollection:
+    return XMMExtMetricCollection(tuple("in/" + n for n in EXT_NAMES), dataset_normalizer, scaling_normalizers, prefix)

@@ -126,7 +126,7 @@ class Model(nn.Module):
             return self.loss(preds, target)
         with torch.no_grad():
             self.loss.update(preds=preds, target=target)
-            if self.in_metrics is not None or self.ext_metrics is not None:
+            if self.in_metrics is not None or self.ext_metrics is not None or self.in_ext_metrics is not None:
                 scale_factor = target.shape[2] / lr_img.shape[2]
                 if scale_factor != 1.0:
                     from xmm_superres_denoise.transforms import ImageUpsample
