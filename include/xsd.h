@@ -294,6 +294,62 @@ int xsd_swinfir_fft_supported(int n);
  * = rfftn(x, norm="ortho"); with inverse set, x += irfftn(spec, s=(H, W), norm="ortho") and spec is overwritten. */
 int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, int H, int W, int C2, int inverse, void* stream);
 
+/* ---- HAT super-resolution, forward only (csrc/hat.hip) ------------------------------------------------------
+ * The reference's HAT (models/transformer/hat.py:10-913; factory models/model.py:216-229, XMM configuration res/configs/models.toml
+ * [hat]: img_size 416, patch_size 16, window_size 16, embed_dim 180, 6 groups of 6 HABs + 1 OCAB with 6 heads, in_chans 1, upscale 2,
+ * overlap_ratio 0.5 -> 24 x 24 keys per 16 x 16 window).  Eval-mode forward in exact fp32 on SwinFIR's kernels (GEMM / conv3x3, window
+ * attention, LayerNorm) plus the overlapping cross-attention, the channel attention and the HAB combine; xsd_set_math does not apply.
+ * No float atomics: outputs are bitwise reproducible and each image's output is independent of the batch it is computed in.
+ * Flat parameter layout: fp32, the order of HAT.parameters() (conv_first.*, patch_embed.norm.* (patch_norm), per layer i:
+ * layers.i.residual_group.blocks.j.{norm1.*, attn.relative_position_bias_table, attn.qkv.weight[, .bias], attn.proj.*,
+ * conv_block.cab.0.*, conv_block.cab.2.*, conv_block.cab.3.attention.1.*, conv_block.cab.3.attention.3.*, norm2.*, mlp.fc1.*, mlp.fc2.*},
+ * layers.i.residual_group.overlap_attn.{relative_position_bias_table, norm1.*, qkv.weight[, .bias], proj.*, norm2.*, mlp.fc1.*,
+ * mlp.fc2.*}, layers.i.conv.* ("1conv"); then norm.*, conv_after_body.* ("1conv"), conv_before_upsample.0.*, upsample.{0,2,..}.*,
+ * conv_last.*).  The buffers relative_position_index_SA / _OCA are not in it: the engine computes both indices, and the shift mask of
+ * the run-time size, from the configuration. */
+typedef struct xsd_hat xsd_hat;
+typedef struct xsd_hat_config {       /* HAT.__init__ arguments (hat.py:642-669) */
+    int32_t img_size[2];           /* (H, W); min(img // patch) must be >= window_size; equal: no block shifts (hat.py:186-189) */
+    int32_t patch_size[2];
+    int32_t in_chans;              /* 1..64 (3: the reference subtracts its RGB mean, hat.py:680-684) */
+    int32_t embed_dim;             /* 2..4096 */
+    int32_t num_layers;            /* 0..16 */
+    int32_t depths[16];            /* 0..64 each */
+    int32_t num_heads[16];         /* divides embed_dim into at most 32 channels per head */
+    int32_t window_size;           /* <= 16 */
+    int32_t compress_ratio;        /* CAB: embed_dim // compress_ratio >= 1 */
+    int32_t squeeze_factor;        /* ChannelAttention: embed_dim // squeeze_factor >= 1 */
+    int32_t qkv_bias;              /* 0/1 */
+    int32_t ape;                   /* must be 0 (refused) */
+    int32_t patch_norm;            /* 0/1 */
+    int32_t upscale;               /* 2, 3, 4, 8 */
+    int32_t upsampler;             /* 0 = "pixelshuffle" (the only one supported); 1 "pixelshuffledirect", 2 "nearest+conv", 3 "" are refused */
+    int32_t resi_connection;       /* 0 = "1conv", 1 = "identity"; anything else (2) is refused */
+    double mlp_ratio;              /* hidden width (int)(embed_dim * mlp_ratio), of the HABs and the OCABs */
+    double qk_scale;               /* 0: head_dim^-0.5 (the reference's `qk_scale or ...`); > 0 as given; < 0 refused */
+    double img_range;              /* > 0 */
+    double conv_scale;             /* weight of the CAB branch (hat.py:268) */
+    double overlap_ratio;          /* overlap window = window_size + (int)(window_size * overlap_ratio): the added part even, the window <= 32 */
+} xsd_hat_config;
+/* replaces HAT.__init__ (engine state only; weights stay in the caller's flat buffer) */
+int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out);
+void xsd_hat_destroy(xsd_hat* r);
+int64_t xsd_hat_param_count(const xsd_hat* r);
+/* the engine's weight-layout step (Linear / conv weights to [taps][cin][cout]); after every parameter update, before forward.
+ * The engine keeps reading dev_params (LayerNorms, bias tables, biases, the squeeze MLP's 1x1 weights) until the next pack. */
+int xsd_hat_pack_weights(xsd_hat* r, const float* dev_params, void* stream);
+/* replaces HAT.forward (hat.py:900-913 with forward_features :875-898, RHAG :603-611, AttenBlocks :493-507, HAB :220-271, OCAB :326-396,
+ * CAB / ChannelAttention :27-44; no clamp there -- Model.forward clamps, models/model.py:48-49).
+ * x: [B][in_chans][H][W], y: [B][in_chans][upscale H][upscale W]; H and W multiples of window_size (the reference does not pad).
+ * A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
+int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* the OCAB's attention on its own (hat.py:334-391 between the qkv Linear and proj): qkv [B][H W][3 C] token rows, table
+ * [(ws + ow - 1)^2][heads] -> out [B][H W][C]; ws <= 16, ws <= ow <= 32, ow - ws even. */
+int xsd_hat_test_ocab(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int ow,
+                      float scale, void* stream);
+/* the channel attention's AdaptiveAvgPool2d(1) on its own (hat.py:20): x [B][HW][C] token-major -> mean [B][C]; synchronises the stream */
+int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_t HW, int C, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

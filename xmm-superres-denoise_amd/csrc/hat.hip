@@ -1,0 +1,696 @@
+// hat.hip -- the reference's HAT super-resolution network (models/transformer/hat.py:10-913), FORWARD ONLY (eval mode: DropPath and
+// the dropouts are identities), in exact fp32, for upsampler "pixelshuffle".
+//
+// The GEMM (Linear / 1x1 / 3x3 conv with its GELU, LeakyReLU, residual, PixelShuffle and NCHW epilogues), the shifted-window attention
+// of the HABs, the LayerNorm and the weight packing are SwinFIR's kernels (sw_kernels.h: this file's copy of them); this file adds what HAT has on top of them.
+// The same rules hold: every product an fp32 FMA, sums over K and all statistics carried in double, no float atomics, every reduction
+// in a fixed order, so an image's output is bitwise independent of the batch it shares and of the run, and a NaN stays in its image.
+//
+// Kernels:
+//   hat_ocab_kernel          the overlapping cross-attention of an OCAB (hat.py:326-391), one workgroup per (window, head): the ws^2
+//                            queries of a window against the ow^2 keys / values of the overlapping window around it (ow = ws +
+//                            int(ws overlap_ratio), stride ws, zero padding (ow - ws) / 2: nn.Unfold), read straight from the qkv token
+//                            rows and written through the window-reverse addressing.  Keys outside the image are zero vectors that
+//                            take part in the softmax with score = bias.  The bias is table[rpi_oca], the index computed here
+//                            (hat.py:805-834, negative indices wrapping as torch's indexing wraps them).  The keys go through LDS in
+//                            chunks of 64, twice: once for the row maxima, once for exp / sum / P V (no rescaling, a fixed order; the chunks' sums in double).
+//   hat_pool_partial_kernel  the first stage of AdaptiveAvgPool2d(1) (hat.py:20): per image, channel and chunk of 256 pixels, a sum in double
+//   hat_ca_kernel            one workgroup per image: the partial sums in chunk order -> the mean, then the squeeze MLP
+//                            conv1x1 -> ReLU -> conv1x1 -> Sigmoid (hat.py:21-24)
+//   hat_combine_kernel       x += (t * y[b, c]) * conv_scale (hat.py:29, :268), and with y null the plain x += t of the "identity" branches
+#include "sw_kernels.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------------
+// overlapping cross-attention
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int OC_KC = 64;        // keys per LDS chunk (two 32-key MFMA tiles)
+constexpr int OC_MAX_OW = 32;    // the overlapping window side the index arithmetic and the launch are checked for
+
+struct OcaP {
+    const float* qkv;            // token rows of 3 C: q, k, v; head h at channels h hd .. h hd + hd - 1 of each (hat.py:334-368)
+    float* o;                    // token rows of C
+    const float* table;          // relative_position_bias_table [(ws + ow - 1)^2][heads]
+    int H, W, C, heads, hd, ws, ow, pad, nwx, nw;
+    float scale;
+};
+
+__global__ __launch_bounds__(512) void hat_ocab_kernel(const OcaP P)
+{
+    __shared__ float Ks[OC_KC][33];
+    __shared__ float Vs[OC_KC][32];
+    const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, i32 = lane & 31, h2 = lane >> 5;
+    const int ws = P.ws, ow = P.ow, NQ = ws * ws, NK = ow * ow, h = blockIdx.y;
+    const int b = (int)blockIdx.x / P.nw, win = (int)blockIdx.x - b * P.nw;
+    const int wy = win / P.nwx, wx = win - wy * P.nwx;
+    const long long HW = (long long)P.H * P.W;
+    const int C3 = 3 * P.C;
+    const int qi = 32 * wave + i32;
+    const bool qok = qi < NQ;
+    const int qy = qi / ws, qx = qi - qy * ws;
+    float qv[16];
+    {
+        const float* row = P.qkv + (qok ? (long long)b * HW + (long long)(wy * ws + qy) * P.W + wx * ws + qx : 0) * C3 + h * P.hd;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int d = 2 * s + h2;
+            qv[s] = (qok && d < P.hd) ? row[d] * P.scale : 0.f;        // q = q * self.scale (hat.py:370)
+        }
+    }
+    // key j of the overlapping window = pixel (wy ws - pad + j / ow, wx ws - pad + j % ow), a zero vector outside the image
+    auto stage = [&](int j0, bool with_v) {
+        for (int e = tid; e < OC_KC * 32; e += nthr) {
+            const int jl = e >> 5, d = e & 31, j = j0 + jl;
+            float kv = 0.f, vv = 0.f;
+            if (j < NK && d < P.hd) {
+                const int ky = j / ow, kx = j - ky * ow;
+                const int y = wy * ws - P.pad + ky, x = wx * ws - P.pad + kx;
+                if (y >= 0 && y < P.H && x >= 0 && x < P.W) {
+                    const float* row = P.qkv + ((long long)b * HW + (long long)y * P.W + x) * C3 + h * P.hd + d;
+                    kv = row[P.C];
+                    if (with_v) vv = row[2 * P.C];
+                }
+            }
+            Ks[jl][d] = kv;
+            if (with_v) Vs[jl][d] = vv;
+        }
+    };
+    // S^T = K (q scale)^T of one 32-key tile plus the bias: acc[v] of lane l = S[query 32 wave + l % 32][key j0 + 32 t + 8 (v / 4) +
+    // 4 (l / 32) + v % 4]; keys past the window's last are -inf
+    const int side = ws + ow - 1, tsize = side * side, off = ws - ow + 1;
+    auto scores = [&](int t, int j0, f32x16& acc) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[v] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            if (2 * s >= P.hd) break;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[32 * t + i32][2 * s + h2], qv[s], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int j = j0 + 32 * t + 8 * (v >> 2) + 4 * h2 + (v & 3);
+            if (j >= NK) acc[v] = -INFINITY;
+            else if (qok) {
+                const int ky = j / ow, kx = j - ky * ow;
+                int idx = (ky - qy + off) * side + (kx - qx + off);            // calculate_rpi_oca (hat.py:820-833)
+                if (idx < 0) idx += tsize;                                      // table[negative index] counts from the end
+                acc[v] += P.table[idx * P.heads + h];
+            }
+        }
+    };
+    f32x16 acc;
+    float mx = -INFINITY;
+    for (int j0 = 0; j0 < NK; j0 += OC_KC) {
+        __syncthreads();
+        stage(j0, false);
+        __syncthreads();
+        for (int t = 0; t < OC_KC / 32 && j0 + 32 * t < NK; ++t) {
+            scores(t, j0, acc);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // per chunk of 64 keys the sum of exp and P V are fp32 chains from zero (P V on the MFMA); the chunks are summed in double
+    double den = 0.0, od[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) od[v] = 0.0;
+    for (int j0 = 0; j0 < NK; j0 += OC_KC) {
+        __syncthreads();
+        stage(j0, true);
+        __syncthreads();
+        float dc = 0.f;
+        f32x16 o;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) o[v] = 0.f;
+        for (int t = 0; t < OC_KC / 32 && j0 + 32 * t < NK; ++t) {
+            scores(t, j0, acc);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const float e = expf(acc[v] - mx);
+                acc[v] = e;
+                dc += e;
+            }
+#pragma unroll
+            for (int v = 0; v < 16; ++v)
+                o = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[v], Vs[32 * t + 8 * (v >> 2) + 4 * h2 + (v & 3)][i32], o, 0, 0, 0);
+        }
+        den += (double)dc;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) od[v] += (double)o[v];
+    }
+    den += __shfl_xor(den, 32);
+    // od[v] of lane l = sum_j e[query r][j] v[j][d = l % 32], r = 8 (v / 4) + 4 (l / 32) + v % 4 of this wave; its denominator is lane r's
+    double dn[16];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) dn[v] = __shfl(den, 8 * (v >> 2) + 4 * h2 + (v & 3));
+    if (i32 >= P.hd) return;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+        const int q = 32 * wave + 8 * (v >> 2) + 4 * h2 + (v & 3);
+        if (q >= NQ) continue;
+        const int oy = q / ws, ox = q - oy * ws;
+        P.o[((long long)b * HW + (long long)(wy * ws + oy) * P.W + wx * ws + ox) * P.C + h * P.hd + i32] = (float)(od[v] / dn[v]);
+    }
+}
+
+hipError_t ocab(hipStream_t s, const float* qkv, float* out, const float* table, int B, int H, int W, int C, int heads, int ws, int ow,
+                float scale)
+{
+    OcaP p{};
+    p.qkv = qkv; p.o = out; p.table = table;
+    p.H = H; p.W = W; p.C = C; p.heads = heads; p.hd = C / heads; p.ws = ws; p.ow = ow; p.pad = (ow - ws) / 2;
+    p.nwx = W / ws; p.nw = (H / ws) * p.nwx;
+    p.scale = scale;
+    const int nqt = (ws * ws + 31) / 32;
+    hipLaunchKernelGGL(hat_ocab_kernel, dim3((unsigned)(B * p.nw), (unsigned)heads), dim3(64 * nqt), 0, s, p);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// channel attention, combine
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int PL_ROWS = 256;     // pixels per partial sum: the chunking depends on H W alone, never on the batch
+
+// x: token-major [B][HW][C]; part: [B][nchunk][C] doubles
+__global__ __launch_bounds__(256) void hat_pool_partial_kernel(const float* x, double* part, long long HW, int C, int nchunk)
+{
+    const int b = blockIdx.y, ch = blockIdx.x;
+    const long long r0 = (long long)ch * PL_ROWS, r1 = r0 + PL_ROWS < HW ? r0 + PL_ROWS : HW;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float* p = x + ((long long)b * HW + r0) * C + c;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        long long r = r0;
+        for (; r + 4 <= r1; r += 4) {
+            s0 += (double)p[0];
+            s1 += (double)p[C];
+            s2 += (double)p[2ll * C];
+            s3 += (double)p[3ll * C];
+            p += 4ll * C;
+        }
+        for (; r < r1; ++r) { s0 += (double)p[0]; p += C; }
+        part[((long long)b * nchunk + ch) * C + c] = (s0 + s1) + (s2 + s3);
+    }
+}
+
+// w1 [Cs][C], w2 [C][Cs] (the 1x1 conv weights as stored); mean_out [B][C] or null; y [B][C] or null (then only the means are made)
+__global__ __launch_bounds__(256) void hat_ca_kernel(const double* part, int nchunk, long long HW, int C, int Cs, const float* w1,
+                                                     const float* b1, const float* w2, const float* b2, float* mean_out, float* y)
+{
+    extern __shared__ float ca_sm[];
+    float* mean = ca_sm;
+    float* hid = ca_sm + C;
+    const int b = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double s = 0.0;
+        for (int k = 0; k < nchunk; ++k) s += part[((long long)b * nchunk + k) * C + c];
+        const float m = (float)(s / (double)HW);
+        mean[c] = m;
+        if (mean_out) mean_out[(long long)b * C + c] = m;
+    }
+    if (!y) return;
+    __syncthreads();
+    for (int j = threadIdx.x; j < Cs; j += 256) {
+        double a = 0.0;
+        for (int c = 0; c < C; ++c) a = fma((double)w1[(long long)j * C + c], (double)mean[c], a);
+        const float v = (float)a + b1[j];
+        hid[j] = v < 0.f ? 0.f : v;                                   // ReLU (a NaN stays a NaN)
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double a = 0.0;
+        for (int j = 0; j < Cs; ++j) a = fma((double)w2[(long long)c * Cs + j], (double)hid[j], a);
+        const float v = (float)a + b2[c];
+        y[(long long)b * C + c] = 1.f / (1.f + expf(-v));
+    }
+}
+
+// x[i] += (t[i] * y[b][c]) * scale, i = (b HW + p) C + c; y null: x[i] += t[i] * scale
+__global__ __launch_bounds__(256) void hat_combine_kernel(float* x, const float* t, const float* y, float scale, long long HWC, int C,
+                                                          long long total)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    float v = t[i];
+    if (y) v = v * y[(i / HWC) * C + (int)(i % C)];
+    x[i] = x[i] + v * scale;
+}
+
+int pool_chunks(long long HW) { return (int)((HW + PL_ROWS - 1) / PL_ROWS); }
+
+hipError_t pool_partial(hipStream_t s, const float* x, double* part, int B, long long HW, int C)
+{
+    const int nchunk = pool_chunks(HW);
+    hipLaunchKernelGGL(hat_pool_partial_kernel, dim3((unsigned)nchunk, (unsigned)B), dim3(256), 0, s, x, part, HW, C, nchunk);
+    return hipGetLastError();
+}
+
+hipError_t combine(hipStream_t s, float* x, const float* t, const float* y, float scale, int B, long long HW, int C)
+{
+    const long long total = (long long)B * HW * C;
+    hipLaunchKernelGGL(hat_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, t, y, scale, HW * C, C, total);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+struct HBlk {                    // HAB (hat.py:141-271)
+    long long n1w, n1b, table, n2w, n2b;
+    Lin qkv, proj, c1, c2, sq1, sq2, fc1, fc2;     // conv_block.cab.0 / .2, cab.3.attention.1 / .3
+    int shift;
+};
+
+struct OBlk {                    // OCAB (hat.py:274-396): its own parameter (the table) comes before its submodules'
+    long long table, n1w, n1b, n2w, n2b;
+    Lin qkv, proj, fc1, fc2;
+};
+
+struct HLayer {
+    std::vector<HBlk> blks;
+    OBlk oca;
+    int heads;
+    Lin conv;                    // "1conv"
+};
+
+} // namespace
+
+struct xsd_hat {
+    xsd_hat_config cfg;
+    int E = 0, hid = 0, Cc = 0, Cs = 0, ws = 0, ow = 0, nfeat = 64;
+    bool noshift = false;
+    long long nparams = 0, wt_floats = 0;
+    long long pen_w = -1, pen_b = -1, norm_w = 0, norm_b = 0;
+    Lin first_l, after, before, last;
+    std::vector<Lin> ups;
+    std::vector<HLayer> layers;
+    std::vector<Lin*> lins;
+    float* wt = nullptr;
+    float* mean = nullptr;
+    const float* params = nullptr;
+    bool packed = false;
+    int B = 0, H = 0, W = 0;
+    char* ws_buf = nullptr;
+    size_t ws_bytes = 0;
+    float *XF = nullptr, *X = nullptr, *A = nullptr, *O = nullptr, *T1 = nullptr, *T2 = nullptr, *V = nullptr, *U0 = nullptr, *U1 = nullptr,
+          *R0 = nullptr, *YC = nullptr, *PART = nullptr;
+
+    ~xsd_hat()
+    {
+        if (wt) hipFree(wt);
+        if (mean) hipFree(mean);
+        if (ws_buf) hipFree(ws_buf);
+    }
+};
+
+namespace {
+
+// the reference's registration order (hat.py:694-783; RHAG / AttenBlocks / HAB / WindowAttention / CAB / ChannelAttention / OCAB / Mlp)
+void layout(xsd_hat* r)
+{
+    const auto& c = r->cfg;
+    const int E = r->E, side = 2 * r->ws - 1, oside = r->ws + r->ow - 1;
+    long long off = 0;
+    lin(r->first_l, off, E, c.in_chans, 9, true);
+    if (c.patch_norm) { r->pen_w = add(off, E); r->pen_b = add(off, E); }
+    for (int li = 0; li < c.num_layers; ++li) {
+        HLayer L;
+        L.heads = c.num_heads[li];
+        for (int j = 0; j < c.depths[li]; ++j) {
+            HBlk k{};
+            k.shift = (j % 2 == 0 || r->noshift) ? 0 : c.window_size / 2;       // AttenBlocks (hat.py:454), HAB (hat.py:186-189)
+            k.n1w = add(off, E); k.n1b = add(off, E);
+            k.table = add(off, (long long)side * side * L.heads);
+            lin(k.qkv, off, 3 * E, E, 1, c.qkv_bias != 0);
+            lin(k.proj, off, E, E, 1, true);
+            lin(k.c1, off, r->Cc, E, 9, true);
+            lin(k.c2, off, E, r->Cc, 9, true);
+            lin(k.sq1, off, r->Cs, E, 1, true);
+            lin(k.sq2, off, E, r->Cs, 1, true);
+            k.n2w = add(off, E); k.n2b = add(off, E);
+            lin(k.fc1, off, r->hid, E, 1, true);
+            lin(k.fc2, off, E, r->hid, 1, true);
+            L.blks.push_back(k);
+        }
+        OBlk& o = L.oca;
+        o.table = add(off, (long long)oside * oside * L.heads);
+        o.n1w = add(off, E); o.n1b = add(off, E);
+        lin(o.qkv, off, 3 * E, E, 1, c.qkv_bias != 0);
+        lin(o.proj, off, E, E, 1, true);
+        o.n2w = add(off, E); o.n2b = add(off, E);
+        lin(o.fc1, off, r->hid, E, 1, true);
+        lin(o.fc2, off, E, r->hid, 1, true);
+        if (c.resi_connection == 0) lin(L.conv, off, E, E, 9, true);
+        r->layers.push_back(L);
+    }
+    r->norm_w = add(off, E); r->norm_b = add(off, E);
+    if (c.resi_connection == 0) lin(r->after, off, E, E, 9, true);
+    lin(r->before, off, r->nfeat, E, 9, true);
+    const int f = up_factor(c.upscale);
+    for (int s = 0; s < up_stages(c.upscale); ++s) {
+        Lin u;
+        lin(u, off, f * f * r->nfeat, r->nfeat, 9, true);
+        r->ups.push_back(u);
+    }
+    lin(r->last, off, c.in_chans, r->nfeat, 9, true);
+    r->nparams = off;
+    // the weights the GEMM reads are packed to [taps][cin][cout]; the squeeze MLP reads its two 1x1 weights as stored
+    r->lins.push_back(&r->first_l);
+    for (auto& L : r->layers) {
+        for (auto& k : L.blks)
+            for (Lin* p : {&k.qkv, &k.proj, &k.c1, &k.c2, &k.fc1, &k.fc2}) r->lins.push_back(p);
+        for (Lin* p : {&L.oca.qkv, &L.oca.proj, &L.oca.fc1, &L.oca.fc2}) r->lins.push_back(p);
+        if (L.conv.cout) r->lins.push_back(&L.conv);
+    }
+    if (r->after.cout) r->lins.push_back(&r->after);
+    r->lins.push_back(&r->before);
+    for (auto& u : r->ups) r->lins.push_back(&u);
+    r->lins.push_back(&r->last);
+    long long t = 0;
+    for (Lin* p : r->lins) p->t = add(t, (long long)p->cout * p->cin * p->taps);
+    r->wt_floats = t;
+}
+
+const float* PP(const xsd_hat* r, long long off) { return off < 0 ? nullptr : r->params + off; }
+
+float qk_scale(const xsd_hat* r, int heads)
+{
+    return r->cfg.qk_scale > 0 ? (float)r->cfg.qk_scale : (float)std::pow((double)(r->E / heads), -0.5);     // `qk_scale or head_dim ** -0.5`
+}
+
+// the HAB's window attention: SwinFIR's kernel; the -100 mask is the one of the run-time size (hat.py:836-865, :880)
+hipError_t hab_attention(xsd_hat* r, hipStream_t s, const HBlk& k, int heads, const float* qkv, float* out)
+{
+    AttnP p{};
+    p.qkv = qkv; p.o = out; p.table = r->params + k.table;
+    p.H = r->H; p.W = r->W; p.C = r->E; p.heads = heads; p.hd = r->E / heads; p.ws = r->ws; p.shift = k.shift;
+    p.nwx = r->W / r->ws; p.nw = (r->H / r->ws) * p.nwx;
+    p.scale = qk_scale(r, heads);
+    dim3 grid((unsigned)(r->B * p.nw), (unsigned)heads);
+    const int nt = (r->ws * r->ws + 31) / 32;
+    switch (nt) {
+#define SW_ATT(T) case T: hipLaunchKernelGGL(sw_attn_kernel<T>, grid, dim3(64 * T), 0, s, p); break;
+    SW_ATT(1) SW_ATT(2) SW_ATT(3) SW_ATT(4) SW_ATT(5) SW_ATT(6) SW_ATT(7) SW_ATT(8)
+#undef SW_ATT
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// workspace of one (B, H, W) in floats; with `assign` set, also the pointers into r->ws_buf
+long long plan_ws(xsd_hat* r, int B, int H, int W, bool assign)
+{
+    const long long HW = (long long)H * W, M = B * HW, E = r->E;
+    const long long up = (long long)r->cfg.upscale * r->cfg.upscale;
+    const long long sizes[12] = {M * E, M * E, M * std::max(3 * E, (long long)r->hid), M * E, M * r->Cc, M * E, M * r->nfeat,
+                                 M * up * r->nfeat, M * up * r->nfeat, M * E, (long long)B * E, 2ll * B * pool_chunks(HW) * E};
+    float** ptrs[12] = {&r->XF, &r->X, &r->A, &r->O, &r->T1, &r->T2, &r->V, &r->U0, &r->U1, &r->R0, &r->YC, &r->PART};
+    long long off = 0;
+    for (int i = 0; i < 12; ++i) {
+        if (assign) *ptrs[i] = (float*)r->ws_buf + off;
+        off += (std::max(sizes[i], 1ll) + 63) / 64 * 64;        // 256-B aligned
+    }
+    return off;
+}
+
+const char* hat_upsampler_name(int u)
+{
+    switch (u) { case 0: return "pixelshuffle"; case 1: return "pixelshuffledirect"; case 2: return "nearest+conv"; default: return "\"\" (none)"; }
+}
+
+} // namespace
+
+extern "C" {
+
+int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out)
+{
+    if (!cfg || !out) return rfail(XSD_ERR_ARG, "null argument");
+    *out = nullptr;
+    const auto& c = *cfg;
+    if (c.ape) return rfail(XSD_ERR_ARG, "HAT: ape=True (absolute position embedding) is not supported by the MI355X engine");
+    if (c.upsampler != 0)
+        return rfail(XSD_ERR_ARG, "HAT: upsampler %s is not supported by the MI355X engine (only \"pixelshuffle\")", hat_upsampler_name(c.upsampler));
+    if (c.resi_connection != 0 && c.resi_connection != 1)
+        return rfail(XSD_ERR_ARG, "HAT: this resi_connection is not supported (only \"1conv\" and \"identity\": the reference has no other branch)");
+    if (c.in_chans < 1 || c.in_chans > 64) return rfail(XSD_ERR_ARG, "HAT: in_chans must be in [1, 64] (got %d)", c.in_chans);
+    if (c.embed_dim < 2 || c.embed_dim > 4096) return rfail(XSD_ERR_ARG, "HAT: embed_dim must be in [2, 4096] (got %d)", c.embed_dim);
+    if (c.num_layers < 0 || c.num_layers > 16) return rfail(XSD_ERR_ARG, "HAT: at most 16 layers (got %d)", c.num_layers);
+    if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
+        return rfail(XSD_ERR_ARG, "HAT: upscale %d is not supported (2^n and 3, modules.py Upsample)", c.upscale);
+    if (!(c.img_range > 0)) return rfail(XSD_ERR_ARG, "HAT: img_range must be positive");
+    if (!(c.qk_scale >= 0))
+        return rfail(XSD_ERR_ARG, "HAT: qk_scale %g is not supported (None / 0 for head_dim^-0.5, or a positive scale)", c.qk_scale);
+    if (!(c.mlp_ratio > 0) || (int)(c.embed_dim * c.mlp_ratio) < 1 || c.embed_dim * c.mlp_ratio > 65536)
+        return rfail(XSD_ERR_ARG, "HAT: mlp_ratio %g gives no usable hidden width", c.mlp_ratio);
+    if (c.img_size[0] < 1 || c.img_size[1] < 1 || c.patch_size[0] < 1 || c.patch_size[1] < 1 || c.window_size < 1)
+        return rfail(XSD_ERR_ARG, "HAT: img_size, patch_size and window_size must be positive");
+    if (c.window_size > 16) return rfail(XSD_ERR_ARG, "HAT: window_size %d exceeds the engine's 16 (256 tokens per window)", c.window_size);
+    const int res = std::min(c.img_size[0] / c.patch_size[0], c.img_size[1] / c.patch_size[1]);
+    if (res < c.window_size)
+        return rfail(XSD_ERR_ARG, "HAT: img_size // patch_size = %d is smaller than window_size %d (the reference's HAB clamps its window, its "
+                     "index table does not follow, and its forward fails)", res, c.window_size);
+    if (!(c.overlap_ratio >= 0) || c.overlap_ratio > 64) return rfail(XSD_ERR_ARG, "HAT: overlap_ratio %g is not supported", c.overlap_ratio);
+    const int ext = (int)(c.window_size * c.overlap_ratio);
+    if (ext % 2) return rfail(XSD_ERR_ARG, "HAT: int(window_size * overlap_ratio) = %d is odd (the reference's unfold then yields the wrong number of "
+                              "windows)", ext);
+    if (c.window_size + ext > OC_MAX_OW)
+        return rfail(XSD_ERR_ARG, "HAT: an overlap window of %d exceeds the engine's %d", c.window_size + ext, OC_MAX_OW);
+    {   // the largest index the reference's shift produces, ws (ws + ow), must lie inside the (ws + ow - 1)^2 table (window 1, no overlap: it does not)
+        const int ow = c.window_size + ext, side = c.window_size + ow - 1;
+        if (c.window_size * (c.window_size + ow) >= side * side)
+            return rfail(XSD_ERR_ARG, "HAT: window_size %d with an overlap window of %d indexes past the OCAB's bias table in the reference", c.window_size, ow);
+    }
+    if (c.compress_ratio < 1 || c.embed_dim / c.compress_ratio < 1)
+        return rfail(XSD_ERR_ARG, "HAT: embed_dim // compress_ratio must be at least 1 (embed_dim %d, compress_ratio %d)", c.embed_dim, c.compress_ratio);
+    if (c.squeeze_factor < 1 || c.embed_dim / c.squeeze_factor < 1)
+        return rfail(XSD_ERR_ARG, "HAT: embed_dim // squeeze_factor must be at least 1 (embed_dim %d, squeeze_factor %d)", c.embed_dim, c.squeeze_factor);
+    for (int l = 0; l < c.num_layers; ++l) {
+        if (c.depths[l] < 0 || c.depths[l] > 64) return rfail(XSD_ERR_ARG, "HAT: depths[%d] must be in [0, 64]", l);
+        const int h = c.num_heads[l];
+        if (h < 1 || c.embed_dim % h) return rfail(XSD_ERR_ARG, "HAT: num_heads[%d] = %d does not divide embed_dim %d", l, h, c.embed_dim);
+        if (c.embed_dim / h > 32) return rfail(XSD_ERR_ARG, "HAT: head dim %d at layer %d; the engine takes at most 32", c.embed_dim / h, l);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return rfail(XSD_ERR_HIP, "no HIP device available");
+    xsd_hat* r = new xsd_hat();
+    r->cfg = c;
+    r->E = c.embed_dim;
+    r->hid = (int)(c.embed_dim * c.mlp_ratio);
+    r->Cc = c.embed_dim / c.compress_ratio;
+    r->Cs = c.embed_dim / c.squeeze_factor;
+    r->ws = c.window_size;
+    r->ow = c.window_size + ext;
+    r->noshift = res <= c.window_size;                       // HAB.__init__ (hat.py:186-189), decided at construction
+    layout(r);
+    std::vector<float> mean(c.in_chans, 0.f);
+    if (c.in_chans == 3) { mean[0] = 0.4488f; mean[1] = 0.4371f; mean[2] = 0.4040f; }   // hat.py:680-684
+    if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
+        hipMalloc((void**)&r->mean, sizeof(float) * c.in_chans) != hipSuccess ||
+        hipMemcpy(r->mean, mean.data(), sizeof(float) * c.in_chans, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        delete r;
+        return rfail(XSD_ERR_NOMEM, "HAT: packed-weight allocation failed");
+    }
+    *out = r;
+    return XSD_OK;
+}
+
+void xsd_hat_destroy(xsd_hat* r) { delete r; }
+
+int64_t xsd_hat_param_count(const xsd_hat* r) { return r ? r->nparams : -1; }
+
+int xsd_hat_pack_weights(xsd_hat* r, const float* dev_params, void* stream)
+{
+    if (!r || !dev_params) return rfail(XSD_ERR_ARG, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    r->params = dev_params;
+    for (const Lin* p : r->lins) {
+        const long long n = (long long)p->cout * p->cin * p->taps;
+        hipLaunchKernelGGL(sw_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dev_params + p->w, r->wt + p->t, p->cout, p->cin, p->taps);
+        hipError_t e = hipGetLastError();
+        if (e) return rfail(XSD_ERR_HIP, "HAT weight packing: %s", hipGetErrorString(e));
+    }
+    r->packed = true;
+    return XSD_OK;
+}
+
+int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream)
+{
+    if (!r || !dev_x || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
+    if (B < 1 || H < 1 || W < 1) return rfail(XSD_ERR_ARG, "bad shape %dx%dx%d", B, H, W);
+    if (B > 65535) return rfail(XSD_ERR_ARG, "HAT: at most 65535 images per call (got %d)", B);
+    if (H % r->ws || W % r->ws)
+        return rfail(XSD_ERR_ARG, "HAT: H and W must be multiples of the window size %d (window_partition; the reference does not pad); got %d x %d",
+                     r->ws, H, W);
+    const long long up = r->cfg.upscale;
+    if ((long long)H * W * up * up > (1ll << 28)) return rfail(XSD_ERR_ARG, "HAT: image of %d x %d pixels is too large", H, W);
+    if (!r->packed) return rfail(XSD_ERR_STATE, "xsd_hat_pack_weights must be called before xsd_hat_forward");
+    hipStream_t s = (hipStream_t)stream;
+    if (r->B != B || r->H != H || r->W != W) {
+        const size_t need = sizeof(float) * (size_t)plan_ws(r, B, H, W, false) + 256;
+        if (need > r->ws_bytes) {
+            // refused BEFORE the held workspace is given up or anything is enqueued: the engine stays usable at its last shape
+            const double gb = 1.0 / (1024.0 * 1024.0 * 1024.0);
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + r->ws_bytes)
+                return rfail(XSD_ERR_NOMEM, "HAT: a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held "
+                             "by this engine of %.1f GiB); use a smaller batch per call", need * gb, B, H, W, free_b * gb, r->ws_bytes * gb, total_b * gb);
+            if (r->ws_buf) { hipDeviceSynchronize(); hipFree(r->ws_buf); r->ws_buf = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
+            hipError_t err = hipMalloc((void**)&r->ws_buf, need);
+            if (err != hipSuccess) {
+                (void)hipGetLastError();
+                return rfail(XSD_ERR_NOMEM, "HAT: workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s", need * gb, B, H, W, hipGetErrorString(err));
+            }
+            r->ws_bytes = need;
+        }
+        plan_ws(r, B, H, W, true);
+        r->B = B; r->H = H; r->W = W;
+    }
+    const auto& c = r->cfg;
+    const int E = r->E, nf = r->nfeat;
+    const long long HW = (long long)H * W, M = B * HW;
+    float* X = r->X;
+    float* O = r->O;
+    float* const XF = r->XF;
+    double* const PART = (double*)r->PART;
+    const int nchunk = pool_chunks(HW);
+    const float* wt = r->wt;
+    hipError_t e = hipSuccess;
+#define HT(x) do { if ((e = (x)) != hipSuccess) return rfail(XSD_ERR_HIP, "HAT forward: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__); } while (0)
+    // x += fc2(gelu(fc1(norm2(x)))) (hat.py:269, :395); O is free
+    auto mlp = [&](long long n2w, long long n2b, const Lin& fc1, const Lin& fc2) -> hipError_t {
+        hipError_t q = ln(s, X, O, PP(r, n2w), PP(r, n2b), M, E);
+        if (q) return q;
+        GemmP p = gp_tok(O, M, E, E, wt + fc1.t, r->hid, PP(r, fc1.b), r->A, r->hid);
+        p.act = ACT_GELU;
+        if ((q = gemm(s, p))) return q;
+        p = gp_tok(r->A, M, r->hid, r->hid, wt + fc2.t, E, PP(r, fc2.b), X, E);
+        p.res = X; p.rbs = 0; p.rps = E;
+        return gemm(s, p);
+    };
+    {   // conv_first over (x - mean) * img_range (hat.py:901-906), NCHW in
+        GemmP p = gp_conv(dev_x, B, H, W, c.in_chans, wt + r->first_l.t, E, PP(r, r->first_l.b), XF, E);
+        p.acs = HW; p.aps = 1;
+        p.isub = r->mean; p.imul = (float)c.img_range;
+        HT(gemm(s, p));
+    }
+    if (c.patch_norm) HT(ln(s, XF, X, PP(r, r->pen_w), PP(r, r->pen_b), M, E));         // patch_embed (hat.py:887)
+    else HT(hipMemcpyAsync(X, XF, sizeof(float) * M * E, hipMemcpyDeviceToDevice, s));
+    for (const HLayer& L : r->layers) {
+        // the RHAG's input: its `+ x` (hat.py:603-611) adds it after the blocks and the conv
+        HT(hipMemcpyAsync(r->R0, X, sizeof(float) * M * E, hipMemcpyDeviceToDevice, s));
+        for (const HBlk& k : L.blks) {
+            // HAB (hat.py:220-271): x = x + proj(attn(u)) + conv_scale * CAB(u), u = norm1(x); then the MLP
+            HT(ln(s, X, O, PP(r, k.n1w), PP(r, k.n1b), M, E));
+            GemmP p = gp_tok(O, M, E, E, wt + k.qkv.t, 3 * E, PP(r, k.qkv.b), r->A, 3 * E);
+            HT(gemm(s, p));
+            p = gp_conv(O, B, H, W, E, wt + k.c1.t, r->Cc, PP(r, k.c1.b), r->T1, r->Cc);       // CAB (hat.py:36-41)
+            p.act = ACT_GELU;
+            HT(gemm(s, p));
+            p = gp_conv(r->T1, B, H, W, r->Cc, wt + k.c2.t, E, PP(r, k.c2.b), r->T2, E);
+            HT(gemm(s, p));
+            HT(pool_partial(s, r->T2, PART, B, HW, E));
+            hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(E + r->Cs), s, PART, nchunk, HW, E, r->Cs,
+                               r->params + k.sq1.w, r->params + k.sq1.b, r->params + k.sq2.w, r->params + k.sq2.b, (float*)nullptr, r->YC);
+            HT(hipGetLastError());
+            HT(hab_attention(r, s, k, L.heads, r->A, O));                                    // u is no longer needed: O takes the attention
+            p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
+            p.res = X; p.rbs = 0; p.rps = E;
+            HT(gemm(s, p));
+            HT(combine(s, X, r->T2, r->YC, (float)c.conv_scale, B, HW, E));
+            HT(mlp(k.n2w, k.n2b, k.fc1, k.fc2));
+        }
+        {   // OCAB (hat.py:326-396)
+            const OBlk& o = L.oca;
+            HT(ln(s, X, O, PP(r, o.n1w), PP(r, o.n1b), M, E));
+            GemmP p = gp_tok(O, M, E, E, wt + o.qkv.t, 3 * E, PP(r, o.qkv.b), r->A, 3 * E);
+            HT(gemm(s, p));
+            HT(ocab(s, r->A, O, r->params + o.table, B, H, W, E, L.heads, r->ws, r->ow, qk_scale(r, L.heads)));
+            p = gp_tok(O, M, E, E, wt + o.proj.t, E, PP(r, o.proj.b), X, E);
+            p.res = X; p.rbs = 0; p.rps = E;
+            HT(gemm(s, p));
+            HT(mlp(o.n2w, o.n2b, o.fc1, o.fc2));
+        }
+        if (c.resi_connection == 0) {
+            GemmP p = gp_conv(X, B, H, W, E, wt + L.conv.t, E, PP(r, L.conv.b), O, E);
+            p.res = r->R0; p.rbs = HW * E; p.rps = E;
+            HT(gemm(s, p));
+            std::swap(X, O);
+        } else {
+            HT(combine(s, X, r->R0, nullptr, 1.f, B, HW, E));
+        }
+    }
+    // norm, conv_after_body + conv_first's output, conv_before_upsample + LeakyReLU(0.01), Upsample, conv_last (hat.py:895, :907-909)
+    HT(ln(s, X, O, PP(r, r->norm_w), PP(r, r->norm_b), M, E));
+    if (c.resi_connection == 0) {
+        GemmP p = gp_conv(O, B, H, W, E, wt + r->after.t, E, PP(r, r->after.b), X, E);
+        p.res = XF; p.rbs = HW * E; p.rps = E;
+        HT(gemm(s, p));
+    } else {
+        HT(combine(s, O, XF, nullptr, 1.f, B, HW, E));
+        std::swap(X, O);
+    }
+    {
+        GemmP p = gp_conv(X, B, H, W, E, wt + r->before.t, nf, PP(r, r->before.b), r->V, nf);
+        p.act = ACT_LRELU; p.slope = 0.01f;
+        HT(gemm(s, p));
+    }
+    const float* cur = r->V;
+    int h = H, w = W;
+    const int f = up_factor(c.upscale);
+    for (size_t i = 0; i < r->ups.size(); ++i) {
+        float* dst = (i % 2 == 0) ? r->U0 : r->U1;
+        GemmP p = gp_conv(cur, B, h, w, nf, wt + r->ups[i].t, f * f * nf, PP(r, r->ups[i].b), dst, nf);
+        p.omode = O_SHUFFLE; p.r = f; p.ybs = (long long)h * w * f * f * nf; p.yps = nf;
+        HT(gemm(s, p));
+        cur = dst; h *= f; w *= f;
+    }
+    {
+        GemmP p = gp_conv(cur, B, h, w, nf, wt + r->last.t, c.in_chans, PP(r, r->last.b), dev_y, 0);
+        p.omode = O_NCHW; p.ybs = (long long)c.in_chans * h * w; p.omean = r->mean; p.orange = (float)c.img_range;
+        HT(gemm(s, p));
+    }
+#undef HT
+    return XSD_OK;
+}
+
+// The OCAB's attention on its own (tests): qkv [B][H W][3 C] token rows, table [(ws + ow - 1)^2][heads] -> out [B][H W][C].
+int xsd_hat_test_ocab(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int ow,
+                      float scale, void* stream)
+{
+    if (!dev_qkv || !dev_table || !dev_out) return rfail(XSD_ERR_ARG, "null argument");
+    if (B < 1 || H < 1 || W < 1 || ws < 1 || ws > 16 || H % ws || W % ws) return rfail(XSD_ERR_ARG, "HAT OCAB test: bad shape");
+    if (heads < 1 || C % heads || C / heads > 32) return rfail(XSD_ERR_ARG, "HAT OCAB test: bad heads");
+    if (ow < ws || ow > OC_MAX_OW || (ow - ws) % 2 || ws * (ws + ow) >= (ws + ow - 1) * (ws + ow - 1))
+        return rfail(XSD_ERR_ARG, "HAT OCAB test: bad overlap window %d", ow);
+    hipError_t e = ocab((hipStream_t)stream, dev_qkv, dev_out, dev_table, B, H, W, C, heads, ws, ow, scale);
+    if (e) return rfail(XSD_ERR_HIP, "HAT OCAB test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+// The channel attention's global average pool on its own (tests): x [B][HW][C] token-major -> mean [B][C].  Synchronises the stream.
+int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_t HW, int C, void* stream)
+{
+    if (!dev_x || !dev_mean) return rfail(XSD_ERR_ARG, "null argument");
+    if (B < 1 || B > 65535 || HW < 1 || C < 1 || C > 4096) return rfail(XSD_ERR_ARG, "HAT pool test: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    const int nchunk = pool_chunks(HW);
+    double* part = nullptr;
+    if (hipMalloc((void**)&part, sizeof(double) * (size_t)B * nchunk * C) != hipSuccess) {
+        (void)hipGetLastError();
+        return rfail(XSD_ERR_NOMEM, "HAT pool test: allocation failed");
+    }
+    hipError_t e = pool_partial(s, dev_x, part, B, HW, C);
+    if (!e) {
+        hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(C + 1), s, part, nchunk, (long long)HW, C, 0,
+                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, dev_mean, (float*)nullptr);
+        e = hipGetLastError();
+    }
+    hipStreamSynchronize(s);
+    hipFree(part);
+    if (e) return rfail(XSD_ERR_HIP, "HAT pool test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+} // extern "C"

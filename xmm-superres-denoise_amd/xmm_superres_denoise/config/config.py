@@ -57,8 +57,8 @@ class ModelCfg(BaseModel):
     name: BaseModels
     memory_efficient: bool
     batch_size: PositiveInt
-    # reference: RrdbCfg | TransformerCfg | RestormerCfg (of the TransformerCfg models, SwinFIR runs on the engine; DRCT and HAT
-    # are refused by Model.configure_model)
+    # reference: RrdbCfg | TransformerCfg | RestormerCfg (of the TransformerCfg models, SwinFIR and HAT run forward on the engine; DRCT
+    # is refused by Model.configure_model, and so is HAT without its forward_only_hat keyword)
     model: Union[RrdbCfg, TransformerCfg, RestormerCfg] = Field(..., discriminator="base_model")
     optimizer: OptimizerCfg
 
@@ -71,7 +71,8 @@ MODELS_TOML = {
                          learning_rate=0.0001, betas=(0.9, 0.999)),
     "swinfir": dict(base_model="swinfir", img_size=416, window_size=16, patch_size=32, embed_dim=180, upsampler="pixelshuffle",
                     in_channels=1, num_heads=[6, 6, 6, 6, 6, 6], depths=[6, 6, 6, 6, 6, 6], learning_rate=0.0002, betas=(0.9, 0.999)),
-    # :32-56 -- configurable, but Model.configure_model refuses both (DRCT's body is dead code in the reference; HAT is not built)
+    # :32-56 -- DRCT is configurable but refused by Model.configure_model (its body is dead code in the reference); HAT is built forward
+    # only: infer.load_model and train.test construct it, a bare configure_model refuses it
     "drct": dict(base_model="drct", img_size=416, window_size=16, patch_size=32, embed_dim=180, upsampler="pixelshuffle",
                  in_channels=1, num_heads=[6, 6, 6, 6, 6, 6], depths=[6, 6, 6, 6, 6, 6], learning_rate=0.0002, betas=(0.9, 0.999)),
     "hat": dict(base_model="hat", img_size=416, window_size=16, patch_size=16, embed_dim=180, upsampler="pixelshuffle",

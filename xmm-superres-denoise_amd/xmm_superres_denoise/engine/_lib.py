@@ -38,6 +38,16 @@ class XsdSwinFIRConfig(ctypes.Structure):
                 ("img_range", ctypes.c_double)]
 
 
+class XsdHATConfig(ctypes.Structure):
+    _fields_ = [("img_size", ctypes.c_int32 * 2), ("patch_size", ctypes.c_int32 * 2), ("in_chans", ctypes.c_int32),
+                ("embed_dim", ctypes.c_int32), ("num_layers", ctypes.c_int32), ("depths", ctypes.c_int32 * 16),
+                ("num_heads", ctypes.c_int32 * 16), ("window_size", ctypes.c_int32), ("compress_ratio", ctypes.c_int32),
+                ("squeeze_factor", ctypes.c_int32), ("qkv_bias", ctypes.c_int32), ("ape", ctypes.c_int32), ("patch_norm", ctypes.c_int32),
+                ("upscale", ctypes.c_int32), ("upsampler", ctypes.c_int32), ("resi_connection", ctypes.c_int32),
+                ("mlp_ratio", ctypes.c_double), ("qk_scale", ctypes.c_double), ("img_range", ctypes.c_double),
+                ("conv_scale", ctypes.c_double), ("overlap_ratio", ctypes.c_double)]
+
+
 def build(force: bool = False) -> str:
     """Compile the HIP sources for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -110,6 +120,15 @@ def load():
     L.xsd_swinfir_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
     L.xsd_swinfir_fft_supported.argtypes = [i32]
     L.xsd_swinfir_test_fft.argtypes = [vp, fp, fp, i32, i32, i32, i32, i32, vp]
+    L.xsd_hat_create.argtypes = [ctypes.POINTER(XsdHATConfig), ctypes.POINTER(vp)]
+    L.xsd_hat_destroy.argtypes = [vp]
+    L.xsd_hat_destroy.restype = None
+    L.xsd_hat_param_count.argtypes = [vp]
+    L.xsd_hat_param_count.restype = i64
+    L.xsd_hat_pack_weights.argtypes = [vp, fp, vp]
+    L.xsd_hat_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
+    L.xsd_hat_test_ocab.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.xsd_hat_test_channel_mean.argtypes = [fp, fp, i32, i64, i32, vp]
     _lib = L
     return L
 
@@ -123,6 +142,8 @@ ABI_SYMBOLS = [
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft",
+    "xsd_hat_create", "xsd_hat_destroy", "xsd_hat_param_count", "xsd_hat_pack_weights", "xsd_hat_forward", "xsd_hat_test_ocab",
+    "xsd_hat_test_channel_mean",
 ]
 
 

@@ -322,6 +322,89 @@ class SwinFIREngine:
         return x
 
 
+class HATEngine:
+    """One HAT engine per module per GPU (xsd_hat_create / _destroy): forward only."""
+
+    UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
+    RESI = ("1conv", "identity")
+
+    def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, compress_ratio: int,
+                 squeeze_factor: int, conv_scale: float, overlap_ratio: float, mlp_ratio: float, qkv_bias: bool, qk_scale, ape: bool,
+                 patch_norm: bool, upscale: int, img_range: float, upsampler: str, resi_connection: str):
+        self.L = _lib.load()
+        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
+        if len(depths) > 16 or len(num_heads) < len(depths):
+            raise XsdError(f"HAT: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
+        cfg = _lib.XsdHATConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
+                                in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
+                                depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
+                                window_size=int(window_size), compress_ratio=int(compress_ratio), squeeze_factor=int(squeeze_factor),
+                                qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)), patch_norm=int(bool(patch_norm)), upscale=int(upscale),
+                                upsampler=self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3,
+                                resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 2,
+                                mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range),
+                                conv_scale=float(conv_scale), overlap_ratio=float(overlap_ratio))
+        h = ctypes.c_void_p()
+        check(self.L.xsd_hat_create(ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+        self.in_chans, self.upscale = int(in_chans), int(upscale)
+        self.nparams = int(self.L.xsd_hat_param_count(self.h))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.xsd_hat_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    @_on_engine_device
+    def pack(self, flat_params: torch.Tensor):
+        _require_cuda_f32(flat_params, "flat_params")
+        if flat_params.numel() != self.nparams:
+            raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
+        self._params_ref = flat_params  # keep alive: the engine reads norms, bias tables, biases and the squeeze MLP from it
+        check(self.L.xsd_hat_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
+
+    @_on_engine_device
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _require_cuda_f32(x, "x")
+        if x.dim() != 4 or x.shape[1] != self.in_chans:
+            raise XsdError(f"x must be [B,{self.in_chans},H,W] (got {tuple(x.shape)})")
+        B, _, H, W = x.shape
+        s = self.upscale
+        y = torch.empty((B, self.in_chans, H * s, W * s), device=x.device, dtype=torch.float32)
+        check(self.L.xsd_hat_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
+        return y
+
+
+@_on_tensor_device
+def hat_ocab_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, heads: int, ws: int, ow: int, scale: float) -> torch.Tensor:
+    """The OCAB's attention on its own (include/xsd.h: xsd_hat_test_ocab): qkv [B, H W, 3 C] token rows (the qkv Linear's output), table
+    [(ws + ow - 1)^2, heads] -> [B, H W, C], the input of proj."""
+    _require_cuda_f32(qkv, "qkv")
+    _require_cuda_f32(table, "table")
+    B, L, C3 = qkv.shape
+    if L != H * W or C3 % 3 or tuple(table.shape) != ((ws + ow - 1) ** 2, heads):
+        raise XsdError(f"qkv {tuple(qkv.shape)} / table {tuple(table.shape)} do not fit {H} x {W}, {heads} heads, windows {ws} / {ow}")
+    out = torch.empty((B, L, C3 // 3), device=qkv.device, dtype=torch.float32)
+    check(_lib.load().xsd_hat_test_ocab(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), B, H, W, C3 // 3, heads, ws, ow, float(scale),
+                                        _stream_ptr(qkv.device)))
+    return out
+
+
+@_on_tensor_device
+def hat_channel_mean(x: torch.Tensor) -> torch.Tensor:
+    """The channel attention's global average pool on its own (include/xsd.h: xsd_hat_test_channel_mean): x [B, HW, C] token-major ->
+    [B, C] means, summed in double in a fixed order."""
+    _require_cuda_f32(x, "x")
+    B, HW, C = x.shape
+    out = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    check(_lib.load().xsd_hat_test_channel_mean(x.data_ptr(), out.data_ptr(), B, HW, C, _stream_ptr(x.device)))
+    return out
+
+
 class ExtMetricsEngine:
     """The extended test metrics of one batch (include/xsd.h: xsd_ext_metrics_eval): gmsd, ms_gmsd, haarpsi, mdsi and the two
     VIF sums per image, as doubles.  The formulas restate piq 0.7.x / torchmetrics 1.x from their published code; parity with

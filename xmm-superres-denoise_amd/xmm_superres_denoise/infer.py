@@ -129,13 +129,15 @@ def wcs_header(in_header, source_file_name: str, res_mult: int, exposure) -> "Or
 
 
 def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, device="cuda:0"):
-    """`Model` of the named factory entry (config.MODELS_TOML: rrdb_denoise, esr_gen, swinfir, restormer) with the weights of a checkpoint in
+    """`Model` of the named factory entry (config.MODELS_TOML: rrdb_denoise, esr_gen, swinfir, hat, restormer) with the weights of a checkpoint in
     the reference's key names, with or without Lightning's `model.` prefix (train.load_checkpoint), on `device`."""
     from xmm_superres_denoise.config.config import model_cfg
     from xmm_superres_denoise.models import Model
     from xmm_superres_denoise.train import load_checkpoint
-    hr_res = lr_res * (2 if name in ("esr_gen", "swinfir") else 1)      # SwinFIR: upscale 2, the class default the factory keeps
+    hr_res = lr_res * (2 if name in ("esr_gen", "swinfir", "hat") else 1)      # SwinFIR, HAT: upscale 2, the class default the factory keeps
     model = Model(model_cfg(name), (lr_res, lr_res), (hr_res, hr_res))
+    if name == "hat":
+        model.configure_model(forward_only_hat=True)      # forward only; a bare configure_model refuses HAT (models/model.py)
     load_checkpoint(checkpoint, model)
     return model.to(device)
 
@@ -143,7 +145,7 @@ def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, d
 @torch.no_grad()
 def infer_file(fits_path, model, det_mask: torch.Tensor | None, out_dir, lr_res: int = 416, lr_max: float = 0.0022336,
                hr_max: float = 0.0005584, stretch: str = "sqrt", device="cuda:0", write_input: bool = True):
-    """Run one det-xy image through `model` (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, or a `Model` of any of them, on `device`).  Returns (prediction [Hout,Wout] in
+    """Run one det-xy image through `model` (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, HAT, or a `Model` of any of them, on `device`).  Returns (prediction [Hout,Wout] in
     physical units, output path).  Mirrors run_inference_on_file.py:127-199 without the exposure bookkeeping against SAS."""
     from xmm_superres_denoise.engine import compose_input, normalize
     data, hdr = read_fits(fits_path)

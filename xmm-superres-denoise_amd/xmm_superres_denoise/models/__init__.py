@@ -1,4 +1,5 @@
 from .model import Model  # noqa: F401
 from .modules.generator_rrdb import GeneratorRRDB_DN, GeneratorRRDB_SR  # noqa: F401
+from .modules.hat import HAT  # noqa: F401
 from .modules.restormer import Restormer  # noqa: F401
 from .modules.swinfir import SwinFIR  # noqa: F401

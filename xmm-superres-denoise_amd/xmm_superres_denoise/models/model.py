@@ -1,5 +1,5 @@
 """`Model`: the reference's LightningModule (models/model.py:13-247) restated without Lightning for the RRDB paths and the
-Restormer and SwinFIR forwards:
+Restormer, SwinFIR and HAT forwards:
 constructor signature, `configure_model` factory (model.py:153-186), `forward` = clamp(generator(x), 0, 1)
 (model.py:48-49 -- the second clamp is fused in the engine's output kernel and is idempotent), `_on_step` / `_on_epoch_end` (model.py:72-150, returning what the reference logs) and `configure_optimizers`
 (model.py:239-247).
@@ -49,16 +49,19 @@ class Model(nn.Module):
     def forward(self, x) -> torch.Tensor:
         if self.model is None:
             self.configure_model()
-        if BaseModels(self.config.name) in (BaseModels.RESTORMER, BaseModels.SWINFIR):
-            # the reference clamps here (model.py:48-49); Restormer and SwinFIR themselves do not (restormer.py:404, swinfir.py:441)
+        if BaseModels(self.config.name) in (BaseModels.RESTORMER, BaseModels.SWINFIR, BaseModels.HAT):
+            # the reference clamps here (model.py:48-49); Restormer, SwinFIR and HAT themselves do not (restormer.py:404, swinfir.py:441,
+            # hat.py:911)
             return torch.clamp(self.model(x), min=0.0, max=1.0)
         # the generator already returns clamp(clamp(.)) == clamp(.)
         return self.model(x)
 
-    def configure_model(self) -> None:
+    def configure_model(self, forward_only_hat: bool = False) -> None:
+        """`forward_only_hat` is TEMPORARY: HAT runs forward only on the engine, and a bare configure_model
+        keeps refusing it by name; infer.load_model and train.test, which never train, pass it as true."""
         if self.model is not None:
             return
-        from xmm_superres_denoise.models import GeneratorRRDB_DN, GeneratorRRDB_SR, Restormer, SwinFIR
+        from xmm_superres_denoise.models import HAT, GeneratorRRDB_DN, GeneratorRRDB_SR, Restormer, SwinFIR
         name = BaseModels(self.config.name)
         if name is BaseModels.ESR_GEN:
             up_scale = self.hr_shape[0] / self.lr_shape[0]
@@ -91,9 +94,16 @@ class Model(nn.Module):
             raise NotImplementedError("drct: DRCT is not on the MI355X engine: in the reference its transformer body is dead code (every "
                                       "RDG returns its input unchanged, drct.py RDG.forward), so a drop-in would be a few convs (SURVEY.md "
                                       "section 8)")
+        elif forward_only_hat:
+            # reference model.py:216-229: everything else is HAT's default (upscale 2, 1conv, overlap_ratio 0.5, ...)
+            m = self.config.model
+            self.model = HAT(img_size=m.img_size, window_size=m.window_size, patch_size=m.patch_size, embed_dim=m.embed_dim,
+                             num_heads=m.num_heads, depths=m.depths, upsampler=m.upsampler, in_chans=m.in_channels,
+                             use_checkpoint=self.config.memory_efficient)
         else:
-            raise NotImplementedError(f"{name}: HAT is not on the MI355X engine (it needs overlapping cross-attention and channel "
-                                      "attention on top of SwinFIR's Swin kernels; SURVEY.md section 8)")
+            raise NotImplementedError(f"{name}: HAT is forward-only on the MI355X engine (csrc/hat.hip), so the training factory does not "
+                                      "build it: use models.HAT directly, infer.load_model(checkpoint, \"hat\") or `train test --model "
+                                      "hat` (they call configure_model(forward_only_hat=True))")
 
     def training_step(self, batch, batch_idx=0):
         return self._on_step(batch, "train")

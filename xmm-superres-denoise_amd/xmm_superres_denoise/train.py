@@ -81,6 +81,9 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
     if name == "swinfir":
         raise NotImplementedError("swinfir: training SwinFIR is not on the MI355X engine (forward only: inference, infer.py, "
                                   "validation / test metrics); fit supports rrdb_denoise and esr_gen")
+    if name == "hat":
+        raise NotImplementedError("hat: training HAT is not on the MI355X engine (forward only: inference, infer.py, "
+                                  "validation / test metrics); fit supports rrdb_denoise and esr_gen")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -155,9 +158,9 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
 def dataset_cfg(dataset_dir, dataset_name="sim_dataset", dataset_type="sim", name="rrdb_denoise", lr_res=416, lr_exps=(20,),
                 hr_exp=100, lr_det_mask=None, hr_det_mask=None, agn=1, lr_bkg=1, comb_hr=False, scaling="sqrt", batch_size=1):
     """the [dataset] section of the reference's run config (res/baseline_config.toml) for `name`: HR at lr_res for the
-    denoiser, 2 x lr_res for esr_gen / swinfir; clamp_max values of the baseline config"""
+    denoiser, 2 x lr_res for esr_gen / swinfir / hat; clamp_max values of the baseline config"""
     from xmm_superres_denoise.config.config import DatasetCfg, HrDatasetCfg, LrDatasetCfg
-    hr_res = lr_res * (2 if name in ("esr_gen", "swinfir") else 1)
+    hr_res = lr_res * (2 if name in ("esr_gen", "swinfir", "hat") else 1)
     return DatasetCfg(directory=dataset_dir, name=dataset_name, type=dataset_type, agn=agn, comb_hr=comb_hr, scaling=scaling,
                       batch_size=batch_size,
                       lr=LrDatasetCfg(bkg=lr_bkg, det_mask=lr_det_mask, exps=list(lr_exps), res=lr_res),
@@ -309,8 +312,8 @@ def main():
     ap = argparse.ArgumentParser(description="fit an RRDB generator with the MI355X engine, on random tiles or an XMM FITS dataset; "
                                              "test a checkpoint on a dataset's test split")
     ap.add_argument("routine", choices=["fit", "test"])
-    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer", "swinfir"],
-                    help="restormer and swinfir are refused: forward only on this engine")
+    ap.add_argument("--model", default="rrdb_denoise", choices=["rrdb_denoise", "esr_gen", "restormer", "swinfir", "hat"],
+                    help="fit refuses restormer, swinfir and hat: forward only on this engine; test takes all five")
     ap.add_argument("--lr-res", type=int, default=416)
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--steps", type=int, default=10)
