@@ -107,6 +107,22 @@ def test_batch_isolation_determinism_and_nan_containment():
         assert torch.equal(yn[i], y[i]), i                         # the others do not see the NaN
 
 
+def test_workspace_growth_and_replan_are_bitwise_neutral():
+    """a larger shape after a smaller one (a larger workspace, new twiddles for H and a new plan), then the smaller one again (a re-plan inside the
+    workspace held): neither leaves a trace in the outputs"""
+    z = np.load(os.path.join(G, "swinfir_b_shifted_odd_w.npz"))
+    cfg = json.loads(str(z["cfg"]))
+    state = gs.make_state(cfg, int(z["seed"]))
+    m, fresh = _module(cfg, state), _module(cfg, state)
+    x1 = torch.from_numpy(gs.make_input((1, 1, 10, 15), 78)).cuda()
+    x2 = torch.from_numpy(gs.make_input((2, 1, 20, 15), 79)).cuda()
+    with torch.no_grad():
+        y1, y2, y3 = m(x1), m(x2), m(x1)
+        only2 = fresh(x2)                                          # a module that has only ever seen x2
+    assert torch.equal(y1, y3)
+    assert torch.equal(y2, only2)
+
+
 def test_model_clamps_and_lightning_checkpoint_and_infer_file(tmp_path):
     from xmm_superres_denoise.config.config import model_cfg
     from xmm_superres_denoise.infer import infer_file, load_model, read_fits, write_fits

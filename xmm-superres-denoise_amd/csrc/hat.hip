@@ -2,9 +2,10 @@
 // the dropouts are identities), in exact fp32, for upsampler "pixelshuffle".
 //
 // The GEMM (Linear / 1x1 / 3x3 conv with its GELU, LeakyReLU, residual, PixelShuffle and NCHW epilogues), the shifted-window attention
-// of the HABs, the LayerNorm and the weight packing are SwinFIR's kernels (sw_kernels.h: this file's copy of them); this file adds what HAT has on top of them.
-// The same rules hold: every product an fp32 FMA, sums over K and all statistics carried in double, no float atomics, every reduction
-// in a fixed order, so an image's output is bitwise independent of the batch it shares and of the run, and a NaN stays in its image.
+// of the HABs, the LayerNorm and the weight packing are the kernels HAT shares with SwinFIR (sw_kernels.h), as is the host code of the
+// head, the MLP half block and the tail; this file adds what HAT has on top of them.  The same rules hold: every product an fp32 FMA,
+// sums over K and all statistics carried in double, no float atomics, every reduction in a fixed order, so an image's output is
+// bitwise independent of the batch it shares and of the run, and a NaN stays in its image.
 //
 // Kernels:
 //   hat_ocab_kernel          the overlapping cross-attention of an OCAB (hat.py:326-391), one workgroup per (window, head): the ws^2
@@ -276,32 +277,12 @@ struct HLayer {
 
 } // namespace
 
-struct xsd_hat {
+struct xsd_hat : SwBase {
     xsd_hat_config cfg;
-    int E = 0, hid = 0, Cc = 0, Cs = 0, ws = 0, ow = 0, nfeat = 64;
+    int Cc = 0, Cs = 0, ow = 0;
     bool noshift = false;
-    long long nparams = 0, wt_floats = 0;
-    long long pen_w = -1, pen_b = -1, norm_w = 0, norm_b = 0;
-    Lin first_l, after, before, last;
-    std::vector<Lin> ups;
     std::vector<HLayer> layers;
-    std::vector<Lin*> lins;
-    float* wt = nullptr;
-    float* mean = nullptr;
-    const float* params = nullptr;
-    bool packed = false;
-    int B = 0, H = 0, W = 0;
-    char* ws_buf = nullptr;
-    size_t ws_bytes = 0;
-    float *XF = nullptr, *X = nullptr, *A = nullptr, *O = nullptr, *T1 = nullptr, *T2 = nullptr, *V = nullptr, *U0 = nullptr, *U1 = nullptr,
-          *R0 = nullptr, *YC = nullptr, *PART = nullptr;
-
-    ~xsd_hat()
-    {
-        if (wt) hipFree(wt);
-        if (mean) hipFree(mean);
-        if (ws_buf) hipFree(ws_buf);
-    }
+    float *T1 = nullptr, *T2 = nullptr, *YC = nullptr, *PART = nullptr;
 };
 
 namespace {
@@ -372,32 +353,6 @@ void layout(xsd_hat* r)
     r->wt_floats = t;
 }
 
-const float* PP(const xsd_hat* r, long long off) { return off < 0 ? nullptr : r->params + off; }
-
-float qk_scale(const xsd_hat* r, int heads)
-{
-    return r->cfg.qk_scale > 0 ? (float)r->cfg.qk_scale : (float)std::pow((double)(r->E / heads), -0.5);     // `qk_scale or head_dim ** -0.5`
-}
-
-// the HAB's window attention: SwinFIR's kernel; the -100 mask is the one of the run-time size (hat.py:836-865, :880)
-hipError_t hab_attention(xsd_hat* r, hipStream_t s, const HBlk& k, int heads, const float* qkv, float* out)
-{
-    AttnP p{};
-    p.qkv = qkv; p.o = out; p.table = r->params + k.table;
-    p.H = r->H; p.W = r->W; p.C = r->E; p.heads = heads; p.hd = r->E / heads; p.ws = r->ws; p.shift = k.shift;
-    p.nwx = r->W / r->ws; p.nw = (r->H / r->ws) * p.nwx;
-    p.scale = qk_scale(r, heads);
-    dim3 grid((unsigned)(r->B * p.nw), (unsigned)heads);
-    const int nt = (r->ws * r->ws + 31) / 32;
-    switch (nt) {
-#define SW_ATT(T) case T: hipLaunchKernelGGL(sw_attn_kernel<T>, grid, dim3(64 * T), 0, s, p); break;
-    SW_ATT(1) SW_ATT(2) SW_ATT(3) SW_ATT(4) SW_ATT(5) SW_ATT(6) SW_ATT(7) SW_ATT(8)
-#undef SW_ATT
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // workspace of one (B, H, W) in floats; with `assign` set, also the pointers into r->ws_buf
 long long plan_ws(xsd_hat* r, int B, int H, int W, bool assign)
 {
@@ -414,11 +369,6 @@ long long plan_ws(xsd_hat* r, int B, int H, int W, bool assign)
     return off;
 }
 
-const char* hat_upsampler_name(int u)
-{
-    switch (u) { case 0: return "pixelshuffle"; case 1: return "pixelshuffledirect"; case 2: return "nearest+conv"; default: return "\"\" (none)"; }
-}
-
 } // namespace
 
 extern "C" {
@@ -430,21 +380,10 @@ int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out)
     const auto& c = *cfg;
     if (c.ape) return rfail(XSD_ERR_ARG, "HAT: ape=True (absolute position embedding) is not supported by the MI355X engine");
     if (c.upsampler != 0)
-        return rfail(XSD_ERR_ARG, "HAT: upsampler %s is not supported by the MI355X engine (only \"pixelshuffle\")", hat_upsampler_name(c.upsampler));
+        return rfail(XSD_ERR_ARG, "HAT: upsampler %s is not supported by the MI355X engine (only \"pixelshuffle\")", upsampler_name(c.upsampler));
     if (c.resi_connection != 0 && c.resi_connection != 1)
         return rfail(XSD_ERR_ARG, "HAT: this resi_connection is not supported (only \"1conv\" and \"identity\": the reference has no other branch)");
-    if (c.in_chans < 1 || c.in_chans > 64) return rfail(XSD_ERR_ARG, "HAT: in_chans must be in [1, 64] (got %d)", c.in_chans);
-    if (c.embed_dim < 2 || c.embed_dim > 4096) return rfail(XSD_ERR_ARG, "HAT: embed_dim must be in [2, 4096] (got %d)", c.embed_dim);
-    if (c.num_layers < 0 || c.num_layers > 16) return rfail(XSD_ERR_ARG, "HAT: at most 16 layers (got %d)", c.num_layers);
-    if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
-        return rfail(XSD_ERR_ARG, "HAT: upscale %d is not supported (2^n and 3, modules.py Upsample)", c.upscale);
-    if (!(c.img_range > 0)) return rfail(XSD_ERR_ARG, "HAT: img_range must be positive");
-    if (!(c.qk_scale >= 0))
-        return rfail(XSD_ERR_ARG, "HAT: qk_scale %g is not supported (None / 0 for head_dim^-0.5, or a positive scale)", c.qk_scale);
-    if (!(c.mlp_ratio > 0) || (int)(c.embed_dim * c.mlp_ratio) < 1 || c.embed_dim * c.mlp_ratio > 65536)
-        return rfail(XSD_ERR_ARG, "HAT: mlp_ratio %g gives no usable hidden width", c.mlp_ratio);
-    if (c.img_size[0] < 1 || c.img_size[1] < 1 || c.patch_size[0] < 1 || c.patch_size[1] < 1 || c.window_size < 1)
-        return rfail(XSD_ERR_ARG, "HAT: img_size, patch_size and window_size must be positive");
+    if (int rc = check_dims(c, "HAT")) return rc;
     if (c.window_size > 16) return rfail(XSD_ERR_ARG, "HAT: window_size %d exceeds the engine's 16 (256 tokens per window)", c.window_size);
     const int res = std::min(c.img_size[0] / c.patch_size[0], c.img_size[1] / c.patch_size[1]);
     if (res < c.window_size)
@@ -465,12 +404,7 @@ int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out)
         return rfail(XSD_ERR_ARG, "HAT: embed_dim // compress_ratio must be at least 1 (embed_dim %d, compress_ratio %d)", c.embed_dim, c.compress_ratio);
     if (c.squeeze_factor < 1 || c.embed_dim / c.squeeze_factor < 1)
         return rfail(XSD_ERR_ARG, "HAT: embed_dim // squeeze_factor must be at least 1 (embed_dim %d, squeeze_factor %d)", c.embed_dim, c.squeeze_factor);
-    for (int l = 0; l < c.num_layers; ++l) {
-        if (c.depths[l] < 0 || c.depths[l] > 64) return rfail(XSD_ERR_ARG, "HAT: depths[%d] must be in [0, 64]", l);
-        const int h = c.num_heads[l];
-        if (h < 1 || c.embed_dim % h) return rfail(XSD_ERR_ARG, "HAT: num_heads[%d] = %d does not divide embed_dim %d", l, h, c.embed_dim);
-        if (c.embed_dim / h > 32) return rfail(XSD_ERR_ARG, "HAT: head dim %d at layer %d; the engine takes at most 32", c.embed_dim / h, l);
-    }
+    if (int rc = check_layers(c, "HAT")) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return rfail(XSD_ERR_HIP, "no HIP device available");
     xsd_hat* r = new xsd_hat();
@@ -485,12 +419,9 @@ int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out)
     layout(r);
     std::vector<float> mean(c.in_chans, 0.f);
     if (c.in_chans == 3) { mean[0] = 0.4488f; mean[1] = 0.4371f; mean[2] = 0.4040f; }   // hat.py:680-684
-    if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
-        hipMalloc((void**)&r->mean, sizeof(float) * c.in_chans) != hipSuccess ||
-        hipMemcpy(r->mean, mean.data(), sizeof(float) * c.in_chans, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
+    if (int rc = alloc_weights(r, "HAT", mean)) {
         delete r;
-        return rfail(XSD_ERR_NOMEM, "HAT: packed-weight allocation failed");
+        return rc;
     }
     *out = r;
     return XSD_OK;
@@ -502,17 +433,7 @@ int64_t xsd_hat_param_count(const xsd_hat* r) { return r ? r->nparams : -1; }
 
 int xsd_hat_pack_weights(xsd_hat* r, const float* dev_params, void* stream)
 {
-    if (!r || !dev_params) return rfail(XSD_ERR_ARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    r->params = dev_params;
-    for (const Lin* p : r->lins) {
-        const long long n = (long long)p->cout * p->cin * p->taps;
-        hipLaunchKernelGGL(sw_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dev_params + p->w, r->wt + p->t, p->cout, p->cin, p->taps);
-        hipError_t e = hipGetLastError();
-        if (e) return rfail(XSD_ERR_HIP, "HAT weight packing: %s", hipGetErrorString(e));
-    }
-    r->packed = true;
-    return XSD_OK;
+    return pack_weights(r, "HAT", dev_params, stream);
 }
 
 int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream)
@@ -528,27 +449,13 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
     if (!r->packed) return rfail(XSD_ERR_STATE, "xsd_hat_pack_weights must be called before xsd_hat_forward");
     hipStream_t s = (hipStream_t)stream;
     if (r->B != B || r->H != H || r->W != W) {
-        const size_t need = sizeof(float) * (size_t)plan_ws(r, B, H, W, false) + 256;
-        if (need > r->ws_bytes) {
-            // refused BEFORE the held workspace is given up or anything is enqueued: the engine stays usable at its last shape
-            const double gb = 1.0 / (1024.0 * 1024.0 * 1024.0);
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + r->ws_bytes)
-                return rfail(XSD_ERR_NOMEM, "HAT: a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held "
-                             "by this engine of %.1f GiB); use a smaller batch per call", need * gb, B, H, W, free_b * gb, r->ws_bytes * gb, total_b * gb);
-            if (r->ws_buf) { hipDeviceSynchronize(); hipFree(r->ws_buf); r->ws_buf = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
-            hipError_t err = hipMalloc((void**)&r->ws_buf, need);
-            if (err != hipSuccess) {
-                (void)hipGetLastError();
-                return rfail(XSD_ERR_NOMEM, "HAT: workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s", need * gb, B, H, W, hipGetErrorString(err));
-            }
-            r->ws_bytes = need;
-        }
+        int rc = grow_ws(r, "HAT", plan_ws(r, B, H, W, false), B, H, W);
+        if (rc) return rc;
         plan_ws(r, B, H, W, true);
         r->B = B; r->H = H; r->W = W;
     }
     const auto& c = r->cfg;
-    const int E = r->E, nf = r->nfeat;
+    const int E = r->E;
     const long long HW = (long long)H * W, M = B * HW;
     float* X = r->X;
     float* O = r->O;
@@ -558,25 +465,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
     const float* wt = r->wt;
     hipError_t e = hipSuccess;
 #define HT(x) do { if ((e = (x)) != hipSuccess) return rfail(XSD_ERR_HIP, "HAT forward: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__); } while (0)
-    // x += fc2(gelu(fc1(norm2(x)))) (hat.py:269, :395); O is free
-    auto mlp = [&](long long n2w, long long n2b, const Lin& fc1, const Lin& fc2) -> hipError_t {
-        hipError_t q = ln(s, X, O, PP(r, n2w), PP(r, n2b), M, E);
-        if (q) return q;
-        GemmP p = gp_tok(O, M, E, E, wt + fc1.t, r->hid, PP(r, fc1.b), r->A, r->hid);
-        p.act = ACT_GELU;
-        if ((q = gemm(s, p))) return q;
-        p = gp_tok(r->A, M, r->hid, r->hid, wt + fc2.t, E, PP(r, fc2.b), X, E);
-        p.res = X; p.rbs = 0; p.rps = E;
-        return gemm(s, p);
-    };
-    {   // conv_first over (x - mean) * img_range (hat.py:901-906), NCHW in
-        GemmP p = gp_conv(dev_x, B, H, W, c.in_chans, wt + r->first_l.t, E, PP(r, r->first_l.b), XF, E);
-        p.acs = HW; p.aps = 1;
-        p.isub = r->mean; p.imul = (float)c.img_range;
-        HT(gemm(s, p));
-    }
-    if (c.patch_norm) HT(ln(s, XF, X, PP(r, r->pen_w), PP(r, r->pen_b), M, E));         // patch_embed (hat.py:887)
-    else HT(hipMemcpyAsync(X, XF, sizeof(float) * M * E, hipMemcpyDeviceToDevice, s));
+    HT(head(s, r, dev_x, c.in_chans, (float)c.img_range, c.patch_norm != 0));          // hat.py:901-906, :887
     for (const HLayer& L : r->layers) {
         // the RHAG's input: its `+ x` (hat.py:603-611) adds it after the blocks and the conv
         HT(hipMemcpyAsync(r->R0, X, sizeof(float) * M * E, hipMemcpyDeviceToDevice, s));
@@ -594,23 +483,24 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(E + r->Cs), s, PART, nchunk, HW, E, r->Cs,
                                r->params + k.sq1.w, r->params + k.sq1.b, r->params + k.sq2.w, r->params + k.sq2.b, (float*)nullptr, r->YC);
             HT(hipGetLastError());
-            HT(hab_attention(r, s, k, L.heads, r->A, O));                                    // u is no longer needed: O takes the attention
+            // u is no longer needed: O takes the attention
+            HT(attention(s, r->A, O, r->params + k.table, B, H, W, E, L.heads, r->ws, k.shift, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
             p.res = X; p.rbs = 0; p.rps = E;
             HT(gemm(s, p));
             HT(combine(s, X, r->T2, r->YC, (float)c.conv_scale, B, HW, E));
-            HT(mlp(k.n2w, k.n2b, k.fc1, k.fc2));
+            HT(mlp(s, r, X, O, M, k.n2w, k.n2b, k.fc1, k.fc2));                              // hat.py:269
         }
         {   // OCAB (hat.py:326-396)
             const OBlk& o = L.oca;
             HT(ln(s, X, O, PP(r, o.n1w), PP(r, o.n1b), M, E));
             GemmP p = gp_tok(O, M, E, E, wt + o.qkv.t, 3 * E, PP(r, o.qkv.b), r->A, 3 * E);
             HT(gemm(s, p));
-            HT(ocab(s, r->A, O, r->params + o.table, B, H, W, E, L.heads, r->ws, r->ow, qk_scale(r, L.heads)));
+            HT(ocab(s, r->A, O, r->params + o.table, B, H, W, E, L.heads, r->ws, r->ow, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + o.proj.t, E, PP(r, o.proj.b), X, E);
             p.res = X; p.rbs = 0; p.rps = E;
             HT(gemm(s, p));
-            HT(mlp(o.n2w, o.n2b, o.fc1, o.fc2));
+            HT(mlp(s, r, X, O, M, o.n2w, o.n2b, o.fc1, o.fc2));                              // hat.py:395
         }
         if (c.resi_connection == 0) {
             GemmP p = gp_conv(X, B, H, W, E, wt + L.conv.t, E, PP(r, L.conv.b), O, E);
@@ -621,7 +511,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             HT(combine(s, X, r->R0, nullptr, 1.f, B, HW, E));
         }
     }
-    // norm, conv_after_body + conv_first's output, conv_before_upsample + LeakyReLU(0.01), Upsample, conv_last (hat.py:895, :907-909)
+    // norm, conv_after_body + conv_first's output, then conv_before_upsample, Upsample, conv_last (hat.py:895, :907-909)
     HT(ln(s, X, O, PP(r, r->norm_w), PP(r, r->norm_b), M, E));
     if (c.resi_connection == 0) {
         GemmP p = gp_conv(O, B, H, W, E, wt + r->after.t, E, PP(r, r->after.b), X, E);
@@ -631,26 +521,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
         HT(combine(s, O, XF, nullptr, 1.f, B, HW, E));
         std::swap(X, O);
     }
-    {
-        GemmP p = gp_conv(X, B, H, W, E, wt + r->before.t, nf, PP(r, r->before.b), r->V, nf);
-        p.act = ACT_LRELU; p.slope = 0.01f;
-        HT(gemm(s, p));
-    }
-    const float* cur = r->V;
-    int h = H, w = W;
-    const int f = up_factor(c.upscale);
-    for (size_t i = 0; i < r->ups.size(); ++i) {
-        float* dst = (i % 2 == 0) ? r->U0 : r->U1;
-        GemmP p = gp_conv(cur, B, h, w, nf, wt + r->ups[i].t, f * f * nf, PP(r, r->ups[i].b), dst, nf);
-        p.omode = O_SHUFFLE; p.r = f; p.ybs = (long long)h * w * f * f * nf; p.yps = nf;
-        HT(gemm(s, p));
-        cur = dst; h *= f; w *= f;
-    }
-    {
-        GemmP p = gp_conv(cur, B, h, w, nf, wt + r->last.t, c.in_chans, PP(r, r->last.b), dev_y, 0);
-        p.omode = O_NCHW; p.ybs = (long long)c.in_chans * h * w; p.omean = r->mean; p.orange = (float)c.img_range;
-        HT(gemm(s, p));
-    }
+    HT(tail(s, r, X, dev_y, c.in_chans, c.upscale, (float)c.img_range));
 #undef HT
     return XSD_OK;
 }

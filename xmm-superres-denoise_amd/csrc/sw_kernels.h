@@ -1,8 +1,24 @@
-// sw_kernels.h -- HAT's copy of the exact-fp32 kernels it shares with SwinFIR: the MFMA GEMM with its conv3x3 mode and epilogues, the
-// (shifted-)window attention, the LayerNorm, the weight packing, and their launch helpers, taken unchanged from swinfir.hip.  Only
-// hat.hip includes this file: swinfir.hip keeps its own definitions, so that SwinFIR's code does not change with HAT's arrival.  A change
-// to one of these kernels belongs in both places (or in a move of swinfir.hip onto this header, checked bitwise on SwinFIR's goldens).
-// Everything is in an anonymous namespace.
+// sw_kernels.h -- the exact-fp32 kernels that the Swin-family networks (swinfir.hip, hat.hip) share, with their launch helpers.
+//
+// Every product is an fp32 FMA on the fp32 matrix instruction v_mfma_f32_32x32x2_f32 (bitwise a k-ordered fmaf chain).  The GEMM's
+// fmaf chains are 16 long, their sums over K are carried in double, as are the LayerNorm statistics.  No float atomics anywhere and
+// every reduction has a fixed order: an image's output is bitwise independent of the batch it shares and of the run.
+//
+// Feature maps are TOKEN-MAJOR ([B][H*W][C], C contiguous): the Swin blocks' (B, L, C) layout, and at the same time the NHWC view
+// that the 3x3 convs read and write through their addressing.
+//
+// Kernels:
+//   sw_gemm_kernel   C = A W (+ bias) on MFMA, 128 x 64 tile per workgroup.  A is either token rows (a Linear / 1x1 conv) or the
+//                    implicit im2col of a 3x3 conv (zero pad 1; NCHW or token-major input, with
+//                    the input affine (x - mean) * img_range of conv_first).  Epilogue: exact-erf GELU or LeakyReLU, residual add
+//                    (may alias the output), and a token-major, PixelShuffle(r) or NCHW (x / img_range + mean) store.
+//   sw_attn_kernel   one workgroup per (window, head): softmax(q scale k^T + table[index] (+ the -100 shift mask)) v, reading q, k,
+//                    v from the qkv rows through the roll / window-partition addressing and writing the same way back.
+//   sw_ln_kernel     LayerNorm over the channels of each token (norm1 / norm2 in front of qkv / fc1, patch_embed.norm, the final
+//                    norm), one wave per token, statistics in double.
+//   sw_pack_kernel   a Linear / conv weight as stored -> the [K][N] matrix sw_gemm_kernel reads.
+//
+// Everything is in an anonymous namespace: each including file compiles its own instance.
 #ifndef XSD_SW_KERNELS_H
 #define XSD_SW_KERNELS_H
 #include <hip/hip_runtime.h>
@@ -364,6 +380,197 @@ hipError_t ln(hipStream_t s, const float* x, float* y, const float* w, const flo
 {
     hipLaunchKernelGGL(sw_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, x, y, w, b, M, C);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side: what the engines of both networks hold and do alike
+// ---------------------------------------------------------------------------------------------------------------
+// `lins` holds pointers into the object that derives from this: such objects live on the heap only and are never copied.
+struct SwBase {
+    int E = 0, hid = 0, ws = 0, nfeat = 64;
+    long long nparams = 0, wt_floats = 0;
+    long long pen_w = -1, pen_b = -1, norm_w = 0, norm_b = 0;
+    Lin first_l, after, before, last;
+    std::vector<Lin> ups;
+    std::vector<Lin*> lins;           // every weight the GEMM reads, in the order of the packed copy
+    float* wt = nullptr;              // the packed copy
+    float* mean = nullptr;
+    const float* params = nullptr;
+    bool packed = false;
+    int B = 0, H = 0, W = 0;          // the shape the workspace is planned for
+    char* ws_buf = nullptr;
+    size_t ws_bytes = 0;
+    float *XF = nullptr, *X = nullptr, *A = nullptr, *O = nullptr, *V = nullptr, *U0 = nullptr, *U1 = nullptr, *R0 = nullptr;
+
+    SwBase() = default;
+    SwBase(const SwBase&) = delete;
+    SwBase& operator=(const SwBase&) = delete;
+    ~SwBase()
+    {
+        if (wt) hipFree(wt);
+        if (mean) hipFree(mean);
+        if (ws_buf) hipFree(ws_buf);
+    }
+};
+
+const float* PP(const SwBase* r, long long off) { return off < 0 ? nullptr : r->params + off; }
+
+const char* upsampler_name(int u)
+{
+    switch (u) { case 0: return "pixelshuffle"; case 1: return "pixelshuffledirect"; case 2: return "nearest+conv"; default: return "\"\" (none)"; }
+}
+
+// the checks of the constructor arguments that both networks share, under the name `net` of the one that asks
+template <class Cfg>
+int check_dims(const Cfg& c, const char* net)
+{
+    if (c.in_chans < 1 || c.in_chans > 64) return rfail(XSD_ERR_ARG, "%s: in_chans must be in [1, 64] (got %d)", net, c.in_chans);
+    if (c.embed_dim < 2 || c.embed_dim > 4096) return rfail(XSD_ERR_ARG, "%s: embed_dim must be in [2, 4096] (got %d)", net, c.embed_dim);
+    if (c.num_layers < 0 || c.num_layers > 16) return rfail(XSD_ERR_ARG, "%s: at most 16 layers (got %d)", net, c.num_layers);
+    if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
+        return rfail(XSD_ERR_ARG, "%s: upscale %d is not supported (2^n and 3, modules.py Upsample)", net, c.upscale);
+    if (!(c.img_range > 0)) return rfail(XSD_ERR_ARG, "%s: img_range must be positive", net);
+    if (!(c.qk_scale >= 0))
+        return rfail(XSD_ERR_ARG, "%s: qk_scale %g is not supported (None / 0 for head_dim^-0.5, or a positive scale)", net, c.qk_scale);
+    if (!(c.mlp_ratio > 0) || (int)(c.embed_dim * c.mlp_ratio) < 1 || c.embed_dim * c.mlp_ratio > 65536)
+        return rfail(XSD_ERR_ARG, "%s: mlp_ratio %g gives no usable hidden width", net, c.mlp_ratio);
+    if (c.img_size[0] < 1 || c.img_size[1] < 1 || c.patch_size[0] < 1 || c.patch_size[1] < 1 || c.window_size < 1)
+        return rfail(XSD_ERR_ARG, "%s: img_size, patch_size and window_size must be positive", net);
+    return XSD_OK;
+}
+
+template <class Cfg>
+int check_layers(const Cfg& c, const char* net)
+{
+    for (int l = 0; l < c.num_layers; ++l) {
+        if (c.depths[l] < 0 || c.depths[l] > 64) return rfail(XSD_ERR_ARG, "%s: depths[%d] must be in [0, 64]", net, l);
+        const int h = c.num_heads[l];
+        if (h < 1 || c.embed_dim % h) return rfail(XSD_ERR_ARG, "%s: num_heads[%d] = %d does not divide embed_dim %d", net, l, h, c.embed_dim);
+        if (c.embed_dim / h > 32) return rfail(XSD_ERR_ARG, "%s: head dim %d at layer %d; the engine takes at most 32", net, c.embed_dim / h, l);
+    }
+    return XSD_OK;
+}
+
+// the packed copy of the weights and the per-channel mean of the input; on failure the caller deletes the engine
+int alloc_weights(SwBase* r, const char* net, const std::vector<float>& mean)
+{
+    if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
+        hipMalloc((void**)&r->mean, sizeof(float) * mean.size()) != hipSuccess ||
+        hipMemcpy(r->mean, mean.data(), sizeof(float) * mean.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return rfail(XSD_ERR_NOMEM, "%s: packed-weight allocation failed", net);
+    }
+    return XSD_OK;
+}
+
+int pack_weights(SwBase* r, const char* net, const float* dev_params, void* stream)
+{
+    if (!r || !dev_params) return rfail(XSD_ERR_ARG, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    r->params = dev_params;
+    for (const Lin* p : r->lins) {
+        const long long n = (long long)p->cout * p->cin * p->taps;
+        hipLaunchKernelGGL(sw_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dev_params + p->w, r->wt + p->t, p->cout, p->cin, p->taps);
+        hipError_t e = hipGetLastError();
+        if (e) return rfail(XSD_ERR_HIP, "%s weight packing: %s", net, hipGetErrorString(e));
+    }
+    r->packed = true;
+    return XSD_OK;
+}
+
+// makes the workspace hold `floats` floats for B tiles of H x W.  The caller then assigns its pointers and sets r->B / H / W.
+int grow_ws(SwBase* r, const char* net, long long floats, int B, int H, int W)
+{
+    const size_t need = sizeof(float) * (size_t)floats + 256;
+    if (need <= r->ws_bytes) return XSD_OK;
+    // refused BEFORE the held workspace is given up or anything is enqueued: the engine stays usable at its last shape
+    const double gb = 1.0 / (1024.0 * 1024.0 * 1024.0);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + r->ws_bytes)
+        return rfail(XSD_ERR_NOMEM, "%s: a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held "
+                     "by this engine of %.1f GiB); use a smaller batch per call", net, need * gb, B, H, W, free_b * gb, r->ws_bytes * gb, total_b * gb);
+    if (r->ws_buf) { hipDeviceSynchronize(); hipFree(r->ws_buf); r->ws_buf = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
+    hipError_t err = hipMalloc((void**)&r->ws_buf, need);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        return rfail(XSD_ERR_NOMEM, "%s: workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s", net, need * gb, B, H, W, hipGetErrorString(err));
+    }
+    r->ws_bytes = need;
+    return XSD_OK;
+}
+
+float attn_scale(double qk_scale, int hd) { return qk_scale > 0 ? (float)qk_scale : (float)std::pow((double)hd, -0.5); }   // `qk_scale or head_dim ** -0.5`
+
+// qkv: token rows of 3 E (the qkv GEMM's output), out: token rows of E.  Both are passed by the caller: the forward's X / O roles
+// change between layers (1conv swaps them), so nothing here may assume which workspace buffer holds what.  With a shift, the -100
+// mask is the one of the run-time size.
+hipError_t attention(hipStream_t s, const float* qkv, float* out, const float* table, int B, int H, int W, int E, int heads, int ws, int shift,
+                     float scale)
+{
+    AttnP p{};
+    p.qkv = qkv; p.o = out; p.table = table;
+    p.H = H; p.W = W; p.C = E; p.heads = heads; p.hd = E / heads; p.ws = ws; p.shift = shift;
+    p.nwx = W / ws; p.nw = (H / ws) * p.nwx;
+    p.scale = scale;
+    dim3 grid((unsigned)(B * p.nw), (unsigned)heads);
+    const int nt = (ws * ws + 31) / 32;
+    switch (nt) {
+#define SW_ATT(T) case T: hipLaunchKernelGGL(sw_attn_kernel<T>, grid, dim3(64 * T), 0, s, p); break;
+    SW_ATT(1) SW_ATT(2) SW_ATT(3) SW_ATT(4) SW_ATT(5) SW_ATT(6) SW_ATT(7) SW_ATT(8)
+#undef SW_ATT
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// conv_first over (x - mean) * img_range, NCHW in, into XF; then patch_embed's norm (or a copy) into X.  For the planned r->B / H / W.
+hipError_t head(hipStream_t s, const SwBase* r, const float* dev_x, int in_chans, float img_range, bool patch_norm)
+{
+    const long long HW = (long long)r->H * r->W, M = r->B * HW;
+    GemmP p = gp_conv(dev_x, r->B, r->H, r->W, in_chans, r->wt + r->first_l.t, r->E, PP(r, r->first_l.b), r->XF, r->E);
+    p.acs = HW; p.aps = 1;
+    p.isub = r->mean; p.imul = img_range;
+    hipError_t e = gemm(s, p);
+    if (e) return e;
+    if (patch_norm) return ln(s, r->XF, r->X, PP(r, r->pen_w), PP(r, r->pen_b), M, r->E);
+    return hipMemcpyAsync(r->X, r->XF, sizeof(float) * M * r->E, hipMemcpyDeviceToDevice, s);
+}
+
+// x += fc2(gelu(fc1(norm2(x)))) on the M token rows of X; O is free, A takes the hidden rows
+hipError_t mlp(hipStream_t s, const SwBase* r, float* X, float* O, long long M, long long n2w, long long n2b, const Lin& fc1, const Lin& fc2)
+{
+    const int E = r->E;
+    hipError_t e = ln(s, X, O, PP(r, n2w), PP(r, n2b), M, E);
+    if (e) return e;
+    GemmP p = gp_tok(O, M, E, E, r->wt + fc1.t, r->hid, PP(r, fc1.b), r->A, r->hid);
+    p.act = ACT_GELU;
+    if ((e = gemm(s, p))) return e;
+    p = gp_tok(r->A, M, r->hid, r->hid, r->wt + fc2.t, E, PP(r, fc2.b), X, E);
+    p.res = X; p.rbs = 0; p.rps = E;
+    return gemm(s, p);
+}
+
+// conv_before_upsample + LeakyReLU(0.01), the PixelShuffle stages of Upsample, conv_last into NCHW x / img_range + mean
+hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, int in_chans, int upscale, float img_range)
+{
+    const int B = r->B, nf = r->nfeat;
+    GemmP p = gp_conv(X, B, r->H, r->W, r->E, r->wt + r->before.t, nf, PP(r, r->before.b), r->V, nf);
+    p.act = ACT_LRELU; p.slope = 0.01f;
+    hipError_t e = gemm(s, p);
+    if (e) return e;
+    const float* cur = r->V;
+    int h = r->H, w = r->W;
+    const int f = up_factor(upscale);
+    for (size_t i = 0; i < r->ups.size(); ++i) {
+        float* dst = (i % 2 == 0) ? r->U0 : r->U1;
+        p = gp_conv(cur, B, h, w, nf, r->wt + r->ups[i].t, f * f * nf, PP(r, r->ups[i].b), dst, nf);
+        p.omode = O_SHUFFLE; p.r = f; p.ybs = (long long)h * w * f * f * nf; p.yps = nf;
+        if ((e = gemm(s, p))) return e;
+        cur = dst; h *= f; w *= f;
+    }
+    p = gp_conv(cur, B, h, w, nf, r->wt + r->last.t, in_chans, PP(r, r->last.b), dev_y, 0);
+    p.omode = O_NCHW; p.ybs = (long long)in_chans * h * w; p.omean = r->mean; p.orange = img_range;
+    return gemm(s, p);
 }
 
 } // namespace

@@ -206,27 +206,30 @@ class Engine:
         return {"mfma_tflops": tf.value, "sclk_ghz": gz.value, "seconds": float(seconds), "fmt": fmt}
 
 
-class RestormerEngine:
-    """One Restormer engine per module per GPU (xsd_restormer_create / _destroy): forward only."""
+class _ForwardEngine:
+    """What the forward-only engines share.  A subclass names its C functions (PREFIX + create / destroy / param_count / pack_weights /
+    forward) and, in _create, its input channels, output channels and the factor between input and output size."""
 
-    def __init__(self, inp_channels: int, out_channels: int, dim: int, num_blocks, num_refinement_blocks: int, heads,
-                 ffn_expansion_factor: float, bias: bool, layernorm_bias_free: bool):
+    PREFIX = ""
+
+    def __init__(self):
         self.L = _lib.load()
-        cfg = _lib.XsdRestormerConfig(inp_channels=inp_channels, out_channels=out_channels, dim=dim,
-                                      num_blocks=(ctypes.c_int32 * 4)(*num_blocks), num_refinement_blocks=num_refinement_blocks,
-                                      heads=(ctypes.c_int32 * 4)(*heads), bias=int(bias), layernorm_bias_free=int(layernorm_bias_free),
-                                      dual_pixel_task=0, ffn_expansion_factor=float(ffn_expansion_factor))
+
+    def _c(self, name: str):
+        return getattr(self.L, self.PREFIX + name)
+
+    def _create(self, cfg, cin: int, cout: int, scale: int):
         h = ctypes.c_void_p()
-        check(self.L.xsd_restormer_create(ctypes.byref(cfg), ctypes.byref(h)))
+        check(self._c("create")(ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
         self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
-        self.in_channels, self.out_channels = int(inp_channels), int(out_channels)
-        self.nparams = int(self.L.xsd_restormer_param_count(self.h))
+        self._cin, self._cout, self._scale = int(cin), int(cout), int(scale)
+        self.nparams = int(self._c("param_count")(self.h))
 
     def __del__(self):
         try:
             if getattr(self, "h", None):
-                self.L.xsd_restormer_destroy(self.h)
+                self._c("destroy")(self.h)
                 self.h = None
         except Exception:
             pass
@@ -236,30 +239,47 @@ class RestormerEngine:
         _require_cuda_f32(flat_params, "flat_params")
         if flat_params.numel() != self.nparams:
             raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
-        self._params_ref = flat_params  # keep alive: the engine reads norms, depthwise / 3x3 weights and biases from it
-        check(self.L.xsd_restormer_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
+        self._params_ref = flat_params  # keep alive: the engine reads from it whatever it does not pack (norms, biases, bias tables, ...)
+        check(self._c("pack_weights")(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
 
     @_on_engine_device
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _require_cuda_f32(x, "x")
-        if x.dim() != 4 or x.shape[1] != self.in_channels:
-            raise XsdError(f"x must be [B,{self.in_channels},H,W] (got {tuple(x.shape)})")
+        if x.dim() != 4 or x.shape[1] != self._cin:
+            raise XsdError(f"x must be [B,{self._cin},H,W] (got {tuple(x.shape)})")
         B, _, H, W = x.shape
-        y = torch.empty((B, self.out_channels, H, W), device=x.device, dtype=torch.float32)
-        check(self.L.xsd_restormer_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
+        y = torch.empty((B, self._cout, H * self._scale, W * self._scale), device=x.device, dtype=torch.float32)
+        check(self._c("forward")(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
         return y
 
 
-class SwinFIREngine:
+class RestormerEngine(_ForwardEngine):
+    """One Restormer engine per module per GPU (xsd_restormer_create / _destroy): forward only."""
+
+    PREFIX = "xsd_restormer_"
+
+    def __init__(self, inp_channels: int, out_channels: int, dim: int, num_blocks, num_refinement_blocks: int, heads,
+                 ffn_expansion_factor: float, bias: bool, layernorm_bias_free: bool):
+        super().__init__()
+        cfg = _lib.XsdRestormerConfig(inp_channels=inp_channels, out_channels=out_channels, dim=dim,
+                                      num_blocks=(ctypes.c_int32 * 4)(*num_blocks), num_refinement_blocks=num_refinement_blocks,
+                                      heads=(ctypes.c_int32 * 4)(*heads), bias=int(bias), layernorm_bias_free=int(layernorm_bias_free),
+                                      dual_pixel_task=0, ffn_expansion_factor=float(ffn_expansion_factor))
+        self._create(cfg, inp_channels, out_channels, 1)
+        self.in_channels, self.out_channels = int(inp_channels), int(out_channels)
+
+
+class SwinFIREngine(_ForwardEngine):
     """One SwinFIR engine per module per GPU (xsd_swinfir_create / _destroy): forward only."""
 
     UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
     RESI = ("SFB", "1conv", "HSFB", "identity")
+    PREFIX = "xsd_swinfir_"
 
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
                  qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
                  resi_connection: str):
-        self.L = _lib.load()
+        super().__init__()
         depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
         if len(depths) > 16 or len(num_heads) < len(depths):
             raise XsdError(f"SwinFIR: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
@@ -271,39 +291,8 @@ class SwinFIREngine:
                                     upsampler=self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3,
                                     resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 3,
                                     mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range))
-        h = ctypes.c_void_p()
-        check(self.L.xsd_swinfir_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self.h = h
-        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+        self._create(cfg, in_chans, in_chans, upscale)
         self.in_chans, self.upscale = int(in_chans), int(upscale)
-        self.nparams = int(self.L.xsd_swinfir_param_count(self.h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.L.xsd_swinfir_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    @_on_engine_device
-    def pack(self, flat_params: torch.Tensor):
-        _require_cuda_f32(flat_params, "flat_params")
-        if flat_params.numel() != self.nparams:
-            raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
-        self._params_ref = flat_params  # keep alive: the engine reads norms, bias tables and biases from it
-        check(self.L.xsd_swinfir_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
-
-    @_on_engine_device
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _require_cuda_f32(x, "x")
-        if x.dim() != 4 or x.shape[1] != self.in_chans:
-            raise XsdError(f"x must be [B,{self.in_chans},H,W] (got {tuple(x.shape)})")
-        B, _, H, W = x.shape
-        s = self.upscale
-        y = torch.empty((B, self.in_chans, H * s, W * s), device=x.device, dtype=torch.float32)
-        check(self.L.xsd_swinfir_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
-        return y
 
     @_on_engine_device
     def fourier_pair(self, x: torch.Tensor, spec: torch.Tensor | None = None) -> torch.Tensor:
@@ -322,16 +311,17 @@ class SwinFIREngine:
         return x
 
 
-class HATEngine:
+class HATEngine(_ForwardEngine):
     """One HAT engine per module per GPU (xsd_hat_create / _destroy): forward only."""
 
     UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
     RESI = ("1conv", "identity")
+    PREFIX = "xsd_hat_"
 
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, compress_ratio: int,
                  squeeze_factor: int, conv_scale: float, overlap_ratio: float, mlp_ratio: float, qkv_bias: bool, qk_scale, ape: bool,
                  patch_norm: bool, upscale: int, img_range: float, upsampler: str, resi_connection: str):
-        self.L = _lib.load()
+        super().__init__()
         depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
         if len(depths) > 16 or len(num_heads) < len(depths):
             raise XsdError(f"HAT: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
@@ -344,39 +334,8 @@ class HATEngine:
                                 resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 2,
                                 mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range),
                                 conv_scale=float(conv_scale), overlap_ratio=float(overlap_ratio))
-        h = ctypes.c_void_p()
-        check(self.L.xsd_hat_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self.h = h
-        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+        self._create(cfg, in_chans, in_chans, upscale)
         self.in_chans, self.upscale = int(in_chans), int(upscale)
-        self.nparams = int(self.L.xsd_hat_param_count(self.h))
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                self.L.xsd_hat_destroy(self.h)
-                self.h = None
-        except Exception:
-            pass
-
-    @_on_engine_device
-    def pack(self, flat_params: torch.Tensor):
-        _require_cuda_f32(flat_params, "flat_params")
-        if flat_params.numel() != self.nparams:
-            raise XsdError(f"flat_params has {flat_params.numel()} elements, engine expects {self.nparams}")
-        self._params_ref = flat_params  # keep alive: the engine reads norms, bias tables, biases and the squeeze MLP from it
-        check(self.L.xsd_hat_pack_weights(self.h, flat_params.data_ptr(), _stream_ptr(flat_params.device)))
-
-    @_on_engine_device
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _require_cuda_f32(x, "x")
-        if x.dim() != 4 or x.shape[1] != self.in_chans:
-            raise XsdError(f"x must be [B,{self.in_chans},H,W] (got {tuple(x.shape)})")
-        B, _, H, W = x.shape
-        s = self.upscale
-        y = torch.empty((B, self.in_chans, H * s, W * s), device=x.device, dtype=torch.float32)
-        check(self.L.xsd_hat_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
-        return y
 
 
 @_on_tensor_device
