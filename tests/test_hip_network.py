@@ -308,7 +308,7 @@ def test_memory_efficient_recompute_matches_full_batch(kind, monkeypatch):
     from xmm_superres_denoise.parallel import DataParallelTrainer
     monkeypatch.setenv("XSD_ME_CHUNK", "2")
     torch.manual_seed(0)
-    ch = 2 if kind == "dn_16_filters_2_channels" else 1        # (16 filters zero-padded to 32, two image channels: Builder::build_multi)
+    ch = 2 if kind == "dn_16_filters_2_channels" else 1        # (16 filters zero-padded to 32, two image channels: the general form of Builder::build)
     mk = (lambda me: GeneratorRRDB_DN(1, 1, 32, 1, memory_efficient=me)) if kind == "dn" else \
          (lambda me: GeneratorRRDB_SR(1, 1, 32, 1, num_upsample=1, memory_efficient=me)) if kind == "sr" else \
          (lambda me: GeneratorRRDB_DN(1, 1, 64, 1, memory_efficient=me)) if kind == "dn_64_filters" else \
@@ -518,7 +518,7 @@ def test_backward_rejects_mismatched_dy_and_stale_generation():
     ("sr", 8, 1, 1, 1, 2, (1, 9, 11)),       # two pixel-shuffle stages
     ("dn", 64, 3, 3, 2, 1, (2, 70, 133)),    # several tiles per image, 320-channel dense convs, RGB with the skip
     ("sr", 48, 1, 1, 1, 1, (1, 21, 45)),     # matrix-instruction path with partial 32-channel blocks (48 .. 240 inputs, 192-channel shuffle conv), ragged against its 8 x 32 tile
-    ("sr", 64, 1, 1, 1, 1, (2, 19, 37)),     # 64 filters, one image channel: the plane kernels with two planes per tensor (Builder::build_multi), shuffle conv 64 -> 256
+    ("sr", 64, 1, 1, 1, 1, (2, 19, 37)),     # 64 filters, one image channel: the plane kernels with two planes per tensor (Builder::build), shuffle conv 64 -> 256
     ("sr", 64, 1, 1, 2, 2, (1, 9, 11)),      # ... two pixel-shuffle stages, two blocks
     ("dn", 96, 1, 1, 1, 1, (1, 17, 40)),     # three planes per tensor: K-loops of up to 15 planes in launches of five
     ("sr", 32, 3, 2, 1, 1, (2, 18, 35)),     # the shipped width with RGB in / two channels out: plane kernels, image-side layers per image channel
@@ -589,10 +589,76 @@ def _widths_vs_float64(kind, nf, in_ch, out_ch, blocks, nup, shape, math=None):
 def test_wide_plane_nets_in_every_math_mode(kind, nf, blocks, nup, shape, math):
     """64, 96, ... 256 filters with one image channel run on the 32-filter configuration's own kernels, a feature tensor being
     2 - 8 planes of 32 channels and a conv's K-loop cut into launches of <= 5 planes that accumulate (csrc/xsd_engine.hip,
-    Builder::build_multi; the dense block's default width is 64, rrdb_blocks.py:23).  Forward, dL/dx and every parameter
+    Builder::build; the dense block's default width is 64, rrdb_blocks.py:23).  Forward, dL/dx and every parameter
     gradient against float64 in each math mode (the 256-filter SR case: eight planes, a 256 -> 1024 shuffle conv, K-loops of
     up to 40 planes)."""
     _widths_vs_float64(kind, nf, 1, 1, blocks, nup, shape, math=math)
+
+
+# (launches, flop, bytes) per profile class (include/xsd.h: xsd_profile_read) of one forward without saved activations ("fwd")
+# and of one forward + backward with dx ("train"), as the commit BEFORE Builder::build and Builder::build_multi became one
+# function gave them: recorded by running this test's body against that commit's library on an MI355X.  Classes without a launch
+# are left out.  0 conv, 1 weight gradient, 2 edge_expand, 3 edge_reduce, 4 edge_wgrad, 7 clamp backward, 8 plane max |x| sweep.
+PLAN_CENSUS_CASES = [
+    ("dn", 32, 1, 1, 2, 1, (2, 24, 40)),     # the shipped configuration: every fast form of the plan
+    ("sr", 32, 1, 1, 1, 2, (1, 19, 22)),     # ... with two 4-output shuffle launches whose maximum the high-resolution plane inherits
+    ("dn", 64, 1, 1, 1, 1, (1, 24, 40)),     # two planes per tensor
+    ("dn", 16, 1, 3, 1, 1, (1, 24, 40)),     # one plane, three output channels: the general form, none of the fast forms
+    ("sr", 32, 3, 2, 1, 1, (1, 17, 23)),     # ... and the shuffle conv as one launch per sub-pixel
+]
+PLAN_CENSUS = {
+    (0, 'f16x3'): {'fwd': {0: (31, 3220439040, 29982720), 2: (1, 1105920, 253440), 3: (1, 1105920, 261120)}, 'train': {0: (62, 6440878080, 59965440), 1: (7, 3220439040, 15237120), 2: (2, 2211840, 506880), 3: (2, 2211840, 529920), 4: (2, 2211840, 506880), 7: (1, 0, 23040)}},
+    (1, 'f16x3'): {'fwd': {0: (19, 631775232, 6366976), 2: (1, 240768, 55176), 3: (1, 3852288, 882816)}, 'train': {0: (38, 1263550464, 12733952), 1: (7, 631775232, 4761856), 2: (2, 4093056, 1794056), 3: (2, 4093056, 964744), 4: (2, 4093056, 937992), 7: (1, 0, 80256), 8: (8, 0, 1070080)}},
+    (2, 'f16x3'): {'fwd': {0: (50, 3255828480, 28753920), 2: (2, 1105920, 253440), 3: (2, 1105920, 261120), 8: (2, 0, 245760)}, 'train': {0: (100, 6511656960, 57507840), 1: (50, 3255828480, 28753920), 2: (4, 2211840, 506880), 3: (4, 2211840, 526080), 4: (4, 2211840, 506880), 7: (1, 0, 11520), 8: (4, 0, 491520)}},
+    (3, 'f16x3'): {'fwd': {0: (16, 813957120, 7618560), 2: (1, 552960, 126720), 3: (3, 1658880, 391680), 8: (1, 0, 122880)}, 'train': {0: (32, 1627914240, 15237120), 1: (16, 813957120, 7618560), 2: (4, 2211840, 752640), 3: (4, 2211840, 529920), 4: (4, 2211840, 506880), 7: (1, 0, 34560), 8: (2, 0, 245760)}},
+    (4, 'f16x3'): {'fwd': {0: (21, 389173248, 3903744), 2: (3, 675648, 254932), 3: (2, 1801728, 412896), 8: (2, 0, 250240)}, 'train': {0: (39, 778346496, 7657344), 1: (18, 389173248, 3753600), 2: (5, 2477376, 1068212), 3: (5, 2477376, 580244), 4: (5, 2477376, 567732), 7: (1, 0, 37536), 8: (7, 0, 650624)}},
+    (0, 'fp32'): {'fwd': {0: (31, 3220439040, 29982720), 2: (1, 1105920, 253440), 3: (1, 1105920, 261120)}, 'train': {0: (62, 6440878080, 59965440), 1: (31, 3220439040, 29982720), 2: (2, 2211840, 506880), 3: (2, 2211840, 529920), 4: (2, 2211840, 506880), 7: (1, 0, 23040)}},
+    (1, 'fp32'): {'fwd': {0: (19, 631775232, 6366976), 2: (1, 240768, 55176), 3: (1, 3852288, 882816)}, 'train': {0: (38, 1263550464, 12733952), 1: (19, 631775232, 6366976), 2: (2, 4093056, 1794056), 3: (2, 4093056, 964744), 4: (2, 4093056, 937992), 7: (1, 0, 80256)}},
+    (2, 'fp32'): {'fwd': {0: (50, 3255828480, 28753920), 2: (2, 1105920, 253440), 3: (2, 1105920, 261120)}, 'train': {0: (100, 6511656960, 57507840), 1: (50, 3255828480, 28753920), 2: (4, 2211840, 506880), 3: (4, 2211840, 526080), 4: (4, 2211840, 506880), 7: (1, 0, 11520)}},
+    (3, 'fp32'): {'fwd': {0: (16, 813957120, 7618560), 2: (1, 552960, 126720), 3: (3, 1658880, 391680)}, 'train': {0: (32, 1627914240, 15237120), 1: (16, 813957120, 7618560), 2: (4, 2211840, 752640), 3: (4, 2211840, 529920), 4: (4, 2211840, 506880), 7: (1, 0, 34560)}},
+    (4, 'fp32'): {'fwd': {0: (21, 389173248, 3903744), 2: (3, 675648, 254932), 3: (2, 1801728, 412896)}, 'train': {0: (39, 778346496, 7657344), 1: (18, 389173248, 3753600), 2: (5, 2477376, 1068212), 3: (5, 2477376, 580244), 4: (5, 2477376, 567732), 7: (1, 0, 37536)}},
+}
+
+
+def _plan_census(kind, nf, in_ch, out_ch, blocks, nup, shape, math):
+    from xmm_superres_denoise.engine import Engine
+    eng = Engine(kind, in_ch, out_ch, nf, blocks, nup)
+    eng.set_math(math)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    params = (torch.rand(eng.nparams, device="cuda", generator=gen) - 0.5) * 0.1
+    eng.pack(params)
+    B, H, W = shape
+    x = torch.rand(B, in_ch, H, W, device="cuda", generator=gen)
+
+    def read():
+        recs = {k: eng.profile_read(k) for k in range(9)}
+        for r in recs.values():
+            assert r["flop"] == int(r["flop"]) and r["bytes"] == int(r["bytes"])      # host-side plan figures: integer-valued doubles
+        return {k: (r["launches"], int(r["flop"]), int(r["bytes"])) for k, r in recs.items() if r["launches"]}
+
+    eng.profile_enable(True)
+    eng.forward(x, save_for_backward=False)
+    fwd = read()
+    eng.profile_enable(True)      # (clears the records)
+    y = eng.forward(x, save_for_backward=True)
+    eng.backward(torch.ones_like(y), torch.empty(eng.nparams, device="cuda"), need_dx=True)
+    train = read()
+    eng.profile_enable(False)
+    return {"fwd": fwd, "train": train}
+
+
+@pytest.mark.parametrize("math", ["f16x3", "fp32"])
+@pytest.mark.parametrize("case", range(len(PLAN_CENSUS_CASES)), ids=lambda i: "%s_nf%d_c%dx%d_b%d_up%d" % PLAN_CENSUS_CASES[i][:6])
+def test_plan_census(case, math):
+    """The launch structure of the plan, which no numeric test sees: how many launches of each kernel class a forward and a
+    training step are, and the flop and bytes the plan books for them (all computed on the host at plan time, so they compare
+    exactly).  Pins the fast forms of the shipped configuration (max |x| reported by edge_expand instead of plane sweeps, one
+    4-output shuffle launch, one pair-list weight-gradient launch per dense block in the split modes) and that the other
+    configurations -- also the one-plane ones with several image channels -- do not take them.  f16x3 has the max |x| slots and
+    sweeps and the block launch, fp32 neither."""
+    got = _plan_census(*PLAN_CENSUS_CASES[case], math)
+    print("PLAN_CENSUS (%d, %r): %r," % (case, math, got))
+    assert got == PLAN_CENSUS[(case, math)]
 
 
 @pytest.mark.parametrize("math", ["f16x3", "bf16x6"])

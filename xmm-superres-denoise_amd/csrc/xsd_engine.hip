@@ -89,7 +89,7 @@ struct xsd_engine {
     int npad = 0;
     std::vector<long long> rrdb_begin_real;
     long long nparams_real = 0;
-    int planes = 1;                  // num_filters / 32: 32-channel planes per feature tensor (1 = the shipped configuration; 2..8: Builder::build_multi)
+    int planes = 1;                  // num_filters / 32: 32-channel planes per feature tensor (1 = the shipped configuration; up to 8: Builder::build)
     long long nparams = 0;
     // flat-param offsets
     long long first_w = 0, first_b = 0, last_w = 0, last_b = 0;
@@ -161,6 +161,10 @@ static hipError_t launch_wgrad_split(int math, int ablate, const WgradParams& p,
     return (math == 4 && !(ablate & (1 << 22))) ? launch_wgrad_h2x(p, s) : launch_wgrad_s3x(p, s);
 }
 
+// Profile classes of xsd_profile_read (include/xsd.h): 0 conv (forward + input-gradient), 1 weight gradient; the HBM-bound kernels:
+// 2 edge_expand (1 -> 32), 3 edge_reduce (32 -> 1), 4 edge_wgrad, 5 L1 loss, 6 Adam, 7 clamp backward, 8 plane max |x| sweeps.
+// `bytes` is ALGORITHMIC traffic (SURVEY 8d rule: every operand once), `flop` 2 x MAC.
+enum { PK_CONV = 0, PK_WGRAD = 1, PK_EDGE_EXPAND = 2, PK_EDGE_REDUCE = 3, PK_EDGE_WGRAD = 4, PK_LOSS = 5, PK_ADAM = 6, PK_CLAMP_BWD = 7, PK_PLANE_AMAX = 8, PK_COUNT = 9 };
 static hipError_t prof_launch(xsd_engine* e, int klass, double flop, double bytes, hipStream_t s, const std::function<hipError_t()>& f)
 {
     if (!e->prof) return f();
@@ -194,10 +198,6 @@ static hipError_t launch_conv_any(xsd_engine* eng, ConvParams& p, hipStream_t s)
     return eng->math == 3 ? launch_conv3x3_s3x(p, s) : launch_conv3x3_mfma(p, s);
 }
 
-// Profile classes of xsd_profile_read (include/xsd.h): 0 conv (forward + input-gradient), 1 weight gradient; the HBM-bound kernels:
-// 2 edge_expand (1 -> 32), 3 edge_reduce (32 -> 1), 4 edge_wgrad, 5 L1 loss, 6 Adam, 7 clamp backward, 8 plane max |x| sweeps.
-// `bytes` is ALGORITHMIC traffic (SURVEY 8d rule: every operand once), `flop` 2 x MAC.
-enum { PK_CONV = 0, PK_WGRAD = 1, PK_EDGE_EXPAND = 2, PK_EDGE_REDUCE = 3, PK_EDGE_WGRAD = 4, PK_LOSS = 5, PK_ADAM = 6, PK_CLAMP_BWD = 7, PK_PLANE_AMAX = 8, PK_COUNT = 9 };
 static hipError_t run_edge_expand(xsd_engine* e, const EdgeExpandParams& p, hipStream_t s)
 {
     const double px = (double)p.B * p.H * p.W;      // reads the image (4 B/px), writes the plane (128); + the plane it adds to; + the mask plane or its compact words
@@ -228,6 +228,7 @@ struct Builder {
     std::vector<std::vector<size_t>> freelist; // per level
     // math mode 4 (f16x3): which plane views have a slot holding their max |x| (set by the producing conv's epilogue or by
     // a plane_amax launch in front of the first consumer); a view dies when its buffer is handed out again
+    typedef std::vector<float*> Tensor;      // a feature tensor: num_filters / 32 planes of 32 channels, in torch.cat's channel order
     typedef std::tuple<uintptr_t, int, int> ViewKey;
     std::map<ViewKey, float*> amax_valid;
     Builder(xsd_engine* e_, int B_, int H_, int W_, bool train_, uintptr_t base_)
@@ -299,11 +300,6 @@ struct Builder {
         if (e->math == 4) invalidate_range(base + off, plane_bytes(level));
         return reinterpret_cast<float*>(base + off);
     }
-    float* alloc1(int level) // 1-channel image
-    {
-        size_t off = top; top += plane_bytes(level, 1); if (top > peak) peak = top;
-        return reinterpret_cast<float*>(base + off);
-    }
     float* alloc_img(int level, int ch) // ch-channel image [B][ch][H][W]
     {
         size_t off = top; top += plane_bytes(level, ch); if (top > peak) peak = top;
@@ -335,6 +331,15 @@ struct Builder {
         p.std_bs = (long long)p.H * p.W * 32;
         for (int j = 0; j < 5; ++j) { p.out[j].a1 = 1.f; p.out[j].a2 = 1.f; p.out[j].slope = 1.f; p.out[j].mslope = 1.f; }
         return p;
+    }
+    WgradParams wgrad_base(int level) const
+    {
+        WgradParams wp;
+        memset(&wp, 0, sizeof(wp));
+        wp.B = B; wp.H = H << level; wp.W = W << level;
+        wp.tilesX = (wp.W + TILE_W - 1) / TILE_W;
+        wp.tilesY = (wp.H + TILE_H - 1) / TILE_H;
+        return wp;
     }
     PlaneIn std_in(const float* p, int level) const
     {
@@ -404,7 +409,7 @@ struct Builder {
             p.ablate = eng->ablate;
             p.zero = eng->zero_page;
             for (auto& f : pre) { hipError_t err = f(s); if (err != hipSuccess) return err; }
-            return prof_launch(eng, 0, flop, bytes, s, [&]() { return launch_conv_any(eng, p, s); });
+            return prof_launch(eng, PK_CONV, flop, bytes, s, [&]() { return launch_conv_any(eng, p, s); });
         };
     }
     // wgrad + fixed-order reduce into the flat gradient vector
@@ -412,10 +417,7 @@ struct Builder {
                       const ConvW& cw, float scale, int j0 = 0, int n0 = 0, int plane = 0)
     {
         xsd_engine* eng = e;
-        WgradParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.B = B; wp.H = H << level; wp.W = W << level;
-        wp.tilesX = (wp.W + TILE_W - 1) / TILE_W; wp.tilesY = (wp.H + TILE_H - 1) / TILE_H;
+        WgradParams wp = wgrad_base(level);
         wp.n_in = (int)xs.size(); wp.n_g = (int)gs.size(); wp.nparts = e->nparts;
 #ifndef XSD_WGRAD_ROUNDS
         // The grid is nparts x n_in x n_g workgroups of one per CU: with nparts = the CU count a launch over k (X, G) pairs runs k
@@ -450,7 +452,7 @@ struct Builder {
             rp.partial = eng->wg_partial; rp.bias_partial = eng->wg_bias_partial;
             rp.dw = eng->b_grads + w_off; rp.db = eng->b_grads + b_off;
             wp.zero = eng->zero_page; wp.ablate = eng->ablate; wp.dbg = eng->dbg;
-            hipError_t err = prof_launch(eng, 1, flop, bytes, s, [&]() { return eng->math >= 3 ? launch_wgrad_split(eng->math, eng->ablate, wp, s) : launch_wgrad_mfma(wp, s); });
+            hipError_t err = prof_launch(eng, PK_WGRAD, flop, bytes, s, [&]() { return eng->math >= 3 ? launch_wgrad_split(eng->math, eng->ablate, wp, s) : launch_wgrad_mfma(wp, s); });
             if (err != hipSuccess) return err;
             return launch_wgrad_reduce(rp, s);
         });
@@ -463,13 +465,10 @@ struct Builder {
     // (DESIGN.md 6.5): bytes are what there is to save; the 16 CUs the launch leaves idle draw next to nothing.
     // Slots are conv-major (conv 5 first), so conv n's blocks are contiguous and each conv gets its own fixed-order reduce.
     static int block_parts_per_xcd(int ncu) { const int m = ncu / 120; return m > 10 ? 10 : m; }     // ((8 m + 1) x 15 partial panels must fit wg_partial's 256 x 5)
-    void wgrad_block_launch(std::vector<Launch>& ops, const float* const xpl[5], const float* const Gp[6], const ConvW* cw, float gscale)
+    void wgrad_block_launch(std::vector<Launch>& ops, const Tensor* const xpl[5], const Tensor* const Gp[6], const ConvW* cw, float gscale)
     {
         xsd_engine* eng = e;
-        WgradParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.B = B; wp.H = H; wp.W = W;
-        wp.tilesX = (wp.W + TILE_W - 1) / TILE_W; wp.tilesY = (wp.H + TILE_H - 1) / TILE_H;
+        WgradParams wp = wgrad_base(0);
         // m parts per XCD, each 15 workgroups side by side: m = CUs / (8 x 15) (MI355X: 256 CUs -> 16 parts = 240 workgroups; the
         // kernel's decode takes any nparts = 8 m or 8 m + 1; the caller falls back to one launch per G when m = 0)
         const int m = block_parts_per_xcd(e->ncu);
@@ -485,7 +484,7 @@ struct Builder {
         if (tail && e->ncu - 120 * m >= 16) wp.nparts = 8 * m + 1;
         std::vector<Launch> pre;
         for (int i = 0; i < 5; ++i) {
-            wp.x[i] = std_in(xpl[i], 0); wp.g[i] = std_in(Gp[i + 1], 0);      // g[n] = G_{n+1}, the gradient at conv n+1's output
+            wp.x[i] = std_in((*xpl[i])[0], 0); wp.g[i] = std_in((*Gp[i + 1])[0], 0);      // g[n] = G_{n+1}, the gradient at conv n+1's output
             if (e->math == 4) {
                 wp.amax_x[i] = slot_of(wp.x[i], wp.H, wp.W, pre);
                 wp.amax_g[i] = slot_of(wp.g[i], wp.H, wp.W, pre);
@@ -515,7 +514,7 @@ struct Builder {
             for (auto& f : pre) { hipError_t perr = f(s); if (perr != hipSuccess) return perr; }
             wp.partial = eng->wg_partial; wp.bias_partial = eng->wg_bias_partial;
             wp.zero = eng->zero_page; wp.ablate = eng->ablate; wp.dbg = eng->dbg;
-            hipError_t err = prof_launch(eng, 1, flop, bytes, s, [&]() { return launch_wgrad_split(eng->math, eng->ablate, wp, s); });
+            hipError_t err = prof_launch(eng, PK_WGRAD, flop, bytes, s, [&]() { return launch_wgrad_split(eng->math, eng->ablate, wp, s); });
             if (err != hipSuccess) return err;
             WgradReduceBatch rb;      // the five convs' fixed-order reductions as one launch (bitwise what five launches gave)
             memset(&rb, 0, sizeof(rb));
@@ -531,266 +530,16 @@ struct Builder {
     }
 
     // ---------------------------------------------------------------------------------------------------------
+    // The RRDB generator, once, for every configuration the plane kernels take: num_filters = 32 P (P = 1..8), 1..8 image channels
+    // -- the shipped net is P = 1, the dense block's own default width is 64 (rrdb_blocks.py:23).  A feature tensor is P planes of
+    // 32 channels in torch.cat's channel order; a conv with 32 a inputs and 32 b outputs is b output chunks, each ONE K-loop
+    // over the a input planes, cut into launches of <= 5 planes: the first launch carries the bias, the later ones add to the
+    // plane it wrote (`accumulate` epilogue), the last one carries the layer's epilogue (residuals, LeakyReLU, masks).  Packed
+    // panels are in [chunk][plane] (forward) / [plane][chunk] (input gradient) order (pack_weights*_kernel).
+    // The shipped configuration (`single`: one plane, one image channel each way) is this schedule plus five fast forms, each
+    // marked `single` below with what it really needs: max |x| reported by edge_expand, compact LeakyReLU' mask words, the
+    // diagnostic batch-chunk sweep, the dense block's pair-list weight-gradient launch, the shuffle conv as one 4-output launch.
     void build()
-    {
-        if (e->planes > 1 || e->cfg.in_channels != 1 || e->cfg.out_channels != 1) { build_multi(); return; }
-        xsd_engine* eng = e;
-        const int blocks = e->cfg.num_res_blocks;
-        const bool sr = e->cfg.kind == XSD_KIND_SR;
-        const int nup = sr ? e->cfg.num_upsample : 0;
-        std::vector<Launch>& F = e->fwd_ops;
-        F.clear();
-        e->bwd_stages.assign(blocks + 2, {});
-
-        struct RdbAct { float* xin; float* xs[4]; float* out; unsigned short* xb[4]; };
-        const bool rdb_bits = train && e->math >= 3;   // compact lrelu' masks of the dense blocks' activations (role-split conv epilogues)
-        std::vector<RdbAct> acts(blocks * 3);
-        std::vector<float*> rin(blocks + 1);
-
-        // ---- forward ------------------------------------------------------------------------------------------
-        float* fea = alloc(0);
-        { // conv_first (generator_rrdb.py:67)
-            EdgeExpandParams p; memset(&p, 0, sizeof(p));
-            p.B = B; p.H = H; p.W = W; p.out = fea; p.w = e->pk_edge + 0; p.mslope = 1.f;
-            p.amax = report_slot(fea, 0);
-            const long long boff = e->first_b;
-            F.push_back([eng, p, boff](hipStream_t s) mutable { p.s = eng->b_x; p.bias = eng->params + boff; return run_edge_expand(eng, p, s); });
-        }
-        float* cur = fea;
-        for (int i = 0; i < blocks; ++i) {
-            rin[i] = cur;
-            for (int r = 0; r < 3; ++r) {
-                RdbAct& a = acts[i * 3 + r];
-                a.xin = cur;
-                ConvParams rp[5];
-                for (int c = 0; c < 5; ++c) {
-                    const ConvW& cw = e->rdb[(i * 3 + r) * 5 + c];
-                    ConvParams p = conv_base(0);
-                    p.n_in = c + 1; p.n_out = 1;
-                    p.in[0] = std_in(a.xin, 0);
-                    for (int k = 0; k < c; ++k) p.in[k + 1] = std_in(a.xs[k], 0);
-                    p.wpanel = fwdp(cw.fwd_off);
-                    float* o = alloc(0);
-                    std_out(p.out[0], o, 0);
-                    if (c < 4) {                                            // rrdb_blocks.py:38-52
-                        p.out[0].slope = 0.2f; a.xs[c] = o;
-                        a.xb[c] = rdb_bits ? reinterpret_cast<unsigned short*>(alloc1(0)) : nullptr;
-                        p.out[0].bits_out = a.xb[c];
-                    }
-                    else {
-                        p.out[0].a1 = 0.2f; p.out[0].e1 = a.xin; p.out[0].s1 = 1.f;           // x5*0.2 + x   (:54)
-                        if (r == 2) { p.out[0].a2 = 0.2f; p.out[0].e2 = rin[i]; p.out[0].s2 = 1.f; } // out*0.2 + x (:70)
-                        a.out = o;
-                    }
-                    rp[c] = p;
-                }
-                // Sweep the dense block in batch chunks: with <= 1-2 images per sweep the block's six planes
-                // (6 x 33.5 MB per 512^2 image) stay in the Infinity Cache between conv_k and conv_{k+1..5}.
-                const int cb = (e->chunk > 0 && e->chunk < B) ? e->chunk : B;
-                for (int b0 = 0; b0 < B; b0 += cb)
-                    for (int c = 0; c < 5; ++c)
-                        F.push_back(conv_launch(slice(rp[c], b0, std::min(cb, B - b0)), true, e->rdb[(i * 3 + r) * 5 + c].b_off));
-                for (int k = 0; k < 4; ++k) release(a.xs[k], 0);
-                if (r > 0) release(a.xin, 0);
-                cur = a.out;
-            }
-            if (i > 0) release(rin[i], 0);
-        }
-        rin[blocks] = cur;
-        float* T = alloc(0);
-        { // fea + trunk_conv(rrdb(fea)) (generator_rrdb.py:68-69)
-            ConvParams p = conv_base(0);
-            p.n_in = 1; p.n_out = 1; p.in[0] = std_in(cur, 0); p.wpanel = fwdp(e->trunk.fwd_off);
-            std_out(p.out[0], T, 0);
-            p.out[0].e1 = fea; p.out[0].s1 = 1.f;
-            F.push_back(conv_launch(p, true, e->trunk.b_off));
-        }
-        if (blocks > 0) release(cur, 0);
-        release(fea, 0);
-
-        std::vector<float*> U(nup, nullptr);
-        float* H1 = nullptr;
-        float* pre = nullptr;
-        const int lo = nup; // output level
-        if (sr) {
-            const float* feat = T;
-            for (int u = 0; u < nup; ++u) { // upsampling: conv 32->128, LeakyReLU(0.01), PixelShuffle(2) (generator_rrdb.py:93-99)
-                U[u] = alloc(u + 1);
-                ConvParams p = conv_base(u);
-                p.n_in = 1; p.n_out = 4; p.in[0] = std_in(feat, u); p.wpanel = fwdp(e->up[u].fwd_off);
-                for (int n = 0; n < 4; ++n) { shuf_out(p.out[n], U[u], u, n); p.out[n].slope = 0.01f; }
-                p.bias = e->pk_sbias + e->up[u].sbias_off;
-                F.push_back(conv_launch(p, false, 0));
-                alias_shuffled(U[u], u);
-                release(const_cast<float*>(feat), u);
-                feat = U[u];
-            }
-            H1 = alloc(lo);
-            { // lrelu(HRconv(fea)) (generator_rrdb.py:107)
-                ConvParams p = conv_base(lo);
-                p.n_in = 1; p.n_out = 1; p.in[0] = std_in(feat, lo); p.wpanel = fwdp(e->hr.fwd_off);
-                std_out(p.out[0], H1, lo); p.out[0].slope = 0.2f;
-                F.push_back(conv_launch(p, true, e->hr.b_off));
-            }
-            if (nup > 0) release(U[nup - 1], lo); else release(T, 0);
-        }
-        pre = train ? alloc1(lo) : nullptr;
-        { // conv_last (+x for DN) + clamp, clamp (generator_rrdb.py:107-108,132-135; model.py:49)
-            EdgeReduceParams p; memset(&p, 0, sizeof(p));
-            p.B = B; p.H = H << lo; p.W = W << lo; p.f = sr ? H1 : T; p.w = e->pk_edge + 2 * 288; p.pre = pre; p.clamp01 = 1;
-            const long long boff = e->last_b;
-            F.push_back([eng, p, boff, sr](hipStream_t s) mutable {
-                p.bias = eng->params + boff; p.skip = sr ? nullptr : eng->b_x; p.y = eng->b_y; return run_edge_reduce(eng, p, s);
-            });
-        }
-        if (!train) return;
-
-        // ---- backward -----------------------------------------------------------------------------------------
-        e->amax_bwd_first = e->amax_used;      // every slot from here on is first written by a backward launch
-        float* dpre = alloc1(lo);
-        float* dT = alloc(0);
-        { // stage 0: output head
-            std::vector<Launch>& S = e->bwd_stages[0];
-            const long long npx = (long long)B * (H << lo) * (W << lo);
-            S.push_back([eng, pre, dpre, npx](hipStream_t s) { return prof_launch(eng, PK_CLAMP_BWD, 0.0, 12.0 * npx, s, [&]() { return launch_clamp_bwd(pre, eng->b_dy, dpre, npx, s); }); });
-            { // conv_last weight grad
-                EdgeWgradParams p; memset(&p, 0, sizeof(p));
-                p.B = B; p.H = H << lo; p.W = W << lo; p.f = sr ? H1 : T; p.s = dpre; p.nblocks = EDGE_WGRAD_BLOCKS;
-                const long long wo = e->last_w, bo = e->last_b;
-                S.push_back([eng, p, wo, bo](hipStream_t s) mutable {
-                    p.partial = eng->edge_partial; return run_edge_wgrad(eng, p, 1, eng->b_grads + wo, eng->b_grads + bo, s);
-                });
-            }
-            if (!sr) {
-                EdgeExpandParams p; memset(&p, 0, sizeof(p));
-                p.B = B; p.H = H; p.W = W; p.s = dpre; p.w = e->pk_edge + 3 * 288; p.out = dT; p.mslope = 1.f;
-                p.amax = report_slot(dT, 0);
-                S.push_back([eng, p](hipStream_t s) { return run_edge_expand(eng, p, s); });
-            } else {
-                float* GH = alloc(lo);
-                { // d(H1) masked by lrelu'(0.2)
-                    EdgeExpandParams p; memset(&p, 0, sizeof(p));
-                    p.B = B; p.H = H << lo; p.W = W << lo; p.s = dpre; p.w = e->pk_edge + 3 * 288; p.out = GH; p.mask = H1; p.mslope = 0.2f;
-                    p.amax = report_slot(GH, lo);
-                    S.push_back([eng, p](hipStream_t s) { return run_edge_expand(eng, p, s); });
-                }
-                const float* hr_in = nup > 0 ? U[nup - 1] : T;
-                wgrad_launch(S, lo, {std_in(hr_in, lo)}, {std_in(GH, lo)}, e->hr, 1.f);
-                float* G = nup > 0 ? alloc(lo) : dT;
-                { // HRconv input gradient (masked by the upsample LeakyReLU(0.01) when it feeds a pixel-shuffle)
-                    ConvParams p = conv_base(lo);
-                    p.n_in = 1; p.n_out = 1; p.in[0] = std_in(GH, lo); p.wpanel = bwdp(e->hr.bwd_off);
-                    std_out(p.out[0], G, lo);
-                    if (nup > 0) { p.out[0].mask = U[nup - 1]; p.out[0].mslope = 0.01f; }
-                    S.push_back(conv_launch(p, false, 0));
-                }
-                for (int u = nup - 1; u >= 0; --u) {
-                    const float* xin = u > 0 ? U[u - 1] : T;
-                    std::vector<PlaneIn> gs;
-                    for (int n = 0; n < 4; ++n) gs.push_back(shuf_in(G, u, n));
-                    wgrad_launch(S, u, {std_in(xin, u)}, gs, e->up[u], 1.f);
-                    float* Gn = u > 0 ? alloc(u) : dT;
-                    ConvParams p = conv_base(u);
-                    p.n_in = 4; p.n_out = 1;
-                    for (int n = 0; n < 4; ++n) p.in[n] = gs[n];
-                    p.wpanel = bwdp(e->up[u].bwd_off);
-                    std_out(p.out[0], Gn, u);
-                    if (u > 0) { p.out[0].mask = U[u - 1]; p.out[0].mslope = 0.01f; }
-                    S.push_back(conv_launch(p, false, 0));
-                    G = Gn;
-                }
-            }
-            // trunk_conv
-            wgrad_launch(S, 0, {std_in(rin[blocks], 0)}, {std_in(dT, 0)}, e->trunk, 1.f);
-        }
-        float* dR = alloc(0);
-        {
-            ConvParams p = conv_base(0);
-            p.n_in = 1; p.n_out = 1; p.in[0] = std_in(dT, 0); p.wpanel = bwdp(e->trunk.bwd_off);
-            std_out(p.out[0], dR, 0);
-            e->bwd_stages[0].push_back(conv_launch(p, false, 0));
-        }
-        float* dS[5] = {nullptr, alloc(0), alloc(0), alloc(0), alloc(0)};
-        for (int i = blocks - 1; i >= 0; --i) {
-            std::vector<Launch>& S = e->bwd_stages[blocks - i];
-            float* dOut = dR;
-            for (int r = 2; r >= 0; --r) {
-                const RdbAct& a = acts[i * 3 + r];
-                const float gscale = r == 2 ? 0.04f : 0.2f;
-                const ConvW* cw = &e->rdb[(i * 3 + r) * 5];
-                dS[0] = alloc(0);
-                const float* xpl[5] = {a.xin, a.xs[0], a.xs[1], a.xs[2], a.xs[3]};
-                // Input-gradients as K-loops (no read-modify-write): dS_j = sum_{c>j} conv^T_c[j](G_c) in ONE launch over
-                // the planes G_5 = dOut, G_4..G_{j+1}; its epilogue adds the residual-path terms (j = 0) or applies
-                // lrelu'(x_j) (j >= 1), which makes dS_j the G_j of conv_j.  conv5's 0.2 / 0.04 factor lives in its
-                // transposed panels (PackDesc.bwd_scale); its weight gradient uses the unscaled dOut and scales in the reduce.
-                const float* Gp[6] = {nullptr, dS[1], dS[2], dS[3], dS[4], dOut}; // G_c, c = 1..5
-                // one pair-list weight-gradient launch per dense block (f16x3 kernel) once every G exists, i.e. in front of dS_0
-                // (XSD_WGRAD_BLOCK=0 restores one launch per G for same-library A/Bs: 122.6 -> 125.6 tiles/s on one device, profiles/r04_ab_wgrad_block_launch.txt)
-#ifdef XSD_TEST_HOOKS
-                static const bool block_wgrad = getenv("XSD_WGRAD_BLOCK") ? atoi(getenv("XSD_WGRAD_BLOCK")) != 0 : true;
-#else
-                constexpr bool block_wgrad = true;
-#endif
-                const bool mega = block_wgrad && e->math >= 3 && block_parts_per_xcd(e->ncu) >= 1;      // both role-split weight-gradient kernels take pair lists; fewer than 120 CUs: one launch per G
-                for (int c = 4; c >= 0; --c) { // conv index c (0-based) = conv_{c+1}
-                    std::vector<PlaneIn> xs;
-                    for (int kk = 0; kk <= c; ++kk) xs.push_back(std_in(xpl[kk], 0));
-                    if (!mega) wgrad_launch(S, 0, xs, {std_in(Gp[c + 1], 0)}, cw[c], c == 4 ? gscale : 1.f);
-                    else if (c == 0) wgrad_block_launch(S, xpl, Gp, cw, gscale);
-                    // now every G needed by dS_c exists: G_5 .. G_{c+1}
-                    const int j = c;
-                    ConvParams p = conv_base(0);
-                    p.n_in = 5 - j; p.n_out = 1;
-                    for (int i = 0; i < 5 - j; ++i) { // step i reads G_{5-i}
-                        const int cc = 5 - i;          // 1-based conv whose gradient plane this is
-                        p.in[i] = std_in(Gp[cc], 0);
-                        p.wstep[i] = bwdp(cw[cc - 1].bwd_off + (long long)j * PANEL_FLOATS);
-                    }
-                    p.wpanel = p.wstep[0];
-                    OutDesc& o = p.out[0];
-                    std_out(o, dS[j], 0);
-                    if (j == 0) {
-                        o.e1 = dOut; o.s1 = r == 2 ? 0.2f : 1.f;
-                        if (r == 0) { o.e2 = dR; o.s2 = 1.f; if (i == 0) { o.e3 = dT; o.s3 = 1.f; } }
-                    } else { o.mask = xpl[j]; o.mslope = 0.2f; o.bits_in = a.xb[j - 1]; }
-                    S.push_back(conv_launch(p, false, 0));
-                }
-                if (dOut != dR) release(dOut, 0, true);
-                dOut = dS[0];
-            }
-            release(dR, 0, true);
-            dR = dOut;
-        }
-        { // last stage: conv_first weight grad and (optionally) dx
-            std::vector<Launch>& S = e->bwd_stages[blocks + 1];
-            float* dFea = dR; // when blocks == 0 this is d(rrdb out) and needs + dT; blocks >= 1 is enforced at create
-            EdgeWgradParams p; memset(&p, 0, sizeof(p));
-            p.B = B; p.H = H; p.W = W; p.f = dFea; p.nblocks = EDGE_WGRAD_BLOCKS;
-            const long long wo = e->first_w, bo = e->first_b;
-            S.push_back([eng, p, wo, bo](hipStream_t s) mutable {
-                p.s = eng->b_x; p.partial = eng->edge_partial; return run_edge_wgrad(eng, p, 0, eng->b_grads + wo, eng->b_grads + bo, s);
-            });
-            EdgeReduceParams q; memset(&q, 0, sizeof(q));
-            q.B = B; q.H = H; q.W = W; q.f = dFea; q.w = e->pk_edge + 1 * 288; q.clamp01 = 0;
-            const float* skipg = sr ? nullptr : dpre;
-            S.push_back([eng, q, skipg](hipStream_t s) mutable {
-                if (!eng->b_dx) return hipSuccess;
-                q.addto = skipg; q.y = eng->b_dx; return run_edge_reduce(eng, q, s);
-            });
-        }
-    }
-
-    // ---------------------------------------------------------------------------------------------------------
-    // Wide nets and image channels: num_filters = 32 P (P = 1..8), 1..8 image channels -- the dense block's own default width is 64
-    // (rrdb_blocks.py:23).  A feature tensor is P planes of 32 channels in torch.cat's channel order; a conv with 32 a
-    // inputs and 32 b outputs is b output chunks, each ONE K-loop over the a input planes, cut into launches of <= 5 planes: the
-    // first launch carries the bias, the later ones add to the plane it wrote (`accumulate` epilogue), the last one carries the
-    // layer's epilogue (residuals, LeakyReLU, masks).  LeakyReLU' masks are read from the activation planes (the compact mask
-    // words have no epilogue variant with `accumulate`).  Same kernels, same packed panels ([chunk][plane] / [plane][chunk]
-    // order, pack_weights*_kernel), same backward stages and flat gradient layout as build().
-    typedef std::vector<float*> Tensor;
-    void build_multi()
     {
         xsd_engine* eng = e;
         const int P = e->planes;
@@ -807,14 +556,18 @@ struct Builder {
         auto last_fwd = [&](int co, int q) { return edge + 288 * (2 * P * CI + co * P + q); };
         auto last_bwd = [&](int co, int q) { return edge + 288 * (2 * P * CI + P * CO + co * P + q); };
         const long long HW = (long long)H * W;
+        const bool single = P == 1 && CI == 1 && CO == 1;
 
         auto alloc_t = [&](int level) { Tensor t(P); for (auto& p : t) p = alloc(level); return t; };
         auto release_t = [&](const Tensor& t, int level, bool force = false) { for (float* p : t) release(p, level, force); };
         auto planes_of = [&](const Tensor& t, int level) { std::vector<PlaneIn> v; for (float* p : t) v.push_back(std_in(p, level)); return v; };
         auto out_desc = [&](float* p, int level) { OutDesc o = conv_base(level).out[0]; std_out(o, p, level); return o; };
+        // row `row` of a conv's packed panels `w`: the n consecutive panels of one K-loop
+        auto panels = [&](const float* w, long long row, int n) { std::vector<const float*> v; for (int k = 0; k < n; ++k) v.push_back(w + (row * n + k) * PANEL_FLOATS); return v; };
         // one output plane: the K-loop over `ins` with the panels `pan` (one per input plane), <= 5 planes per launch
+        // (nb > 0: restricted to the images [b0, b0 + nb))
         auto kloop = [&](std::vector<Launch>& ops, int level, const std::vector<PlaneIn>& ins, const std::vector<const float*>& pan,
-                         const OutDesc& fin, bool bias_from_params, long long bias_off, const float* bias_ptr) {
+                         const OutDesc& fin, bool bias_from_params, long long bias_off, const float* bias_ptr, int b0 = 0, int nb = 0) {
             const int n = (int)ins.size();
             for (int base = 0; base < n; base += 5) {
                 const int cnt = std::min(5, n - base);
@@ -828,7 +581,7 @@ struct Builder {
                 else { o.p = fin.p; o.ps = fin.ps; o.rs = fin.rs; o.bs = fin.bs; o.a1 = fin.a1; }   // partial sums carry the final scale
                 o.accumulate = first ? 0 : 1;
                 if (first) p.bias = bias_ptr;
-                ops.push_back(conv_launch(p, first && bias_from_params, bias_off));
+                ops.push_back(conv_launch(nb ? slice(p, b0, nb) : p, first && bias_from_params, bias_off));
             }
         };
         // weight gradient of one conv: per output chunk, the input planes in groups of <= 5
@@ -839,8 +592,11 @@ struct Builder {
                     wgrad_launch(ops, level, grp, {std_in(g[q], level)}, cw, scale, base, q, 0);
                 }
         };
-        struct RdbActM { Tensor xin, xs[4], out; };
-        std::vector<RdbActM> acts(blocks * 3);
+        struct RdbAct { Tensor xin, xs[4], out; unsigned short* xb[4] = {}; };
+        // compact lrelu' mask words of the dense blocks' activations (role-split conv epilogues) instead of the activation planes as masks.
+        // `single`; needs P == 1: the epilogue that writes / reads the words has no `accumulate` variant, so the K-loop must be one launch
+        const bool rdb_bits = single && train && e->math >= 3;
+        std::vector<RdbAct> acts(blocks * 3);
         std::vector<Tensor> rin(blocks + 1);
 
         // ---- forward ------------------------------------------------------------------------------------------
@@ -849,6 +605,9 @@ struct Builder {
             for (int ch = 0; ch < CI; ++ch) {
                 EdgeExpandParams p; memset(&p, 0, sizeof(p));
                 p.B = B; p.H = H; p.W = W; p.out = fea[q]; p.w = first_fwd(ch, q); p.mslope = 1.f; p.s_bs = CI * HW; p.accumulate = ch > 0;
+                // `single`; needs CI == 1: the kernel reports the maximum of what it WRITES and so refuses `amax` with `accumulate`
+                // (partial sums); elsewhere the first consumer sweeps the plane (plane_amax)
+                if (single) p.amax = report_slot(fea[q], 0);
                 const long long boff = e->first_b + 32 * q, xo = ch * HW;
                 F.push_back([eng, p, boff, xo, ch](hipStream_t s) mutable {
                     p.s = eng->b_x + xo; p.bias = ch == 0 ? eng->params + boff : nullptr; return run_edge_expand(eng, p, s); });
@@ -857,27 +616,32 @@ struct Builder {
         for (int i = 0; i < blocks; ++i) {
             rin[i] = cur;
             for (int r = 0; r < 3; ++r) {
-                RdbActM& a = acts[i * 3 + r];
+                RdbAct& a = acts[i * 3 + r];
                 a.xin = cur;
                 for (int c = 0; c < 5; ++c) {
-                    const ConvW& cw = e->rdb[(i * 3 + r) * 5 + c];
-                    const int ns = (c + 1) * P;
-                    std::vector<PlaneIn> ins;
-                    for (int t = 0; t <= c; ++t) for (float* pl : (t == 0 ? a.xin : a.xs[t - 1])) ins.push_back(std_in(pl, 0));
-                    Tensor o = alloc_t(0);
-                    for (int q = 0; q < P; ++q) {
-                        std::vector<const float*> pan;
-                        for (int k = 0; k < ns; ++k) pan.push_back(fwdp(cw.fwd_off + ((long long)q * ns + k) * PANEL_FLOATS));
-                        OutDesc fin = out_desc(o[q], 0);
-                        if (c < 4) fin.slope = 0.2f;                                                   // rrdb_blocks.py:38-52
-                        else {
-                            fin.a1 = 0.2f; fin.e1 = a.xin[q]; fin.s1 = 1.f;                            // x5*0.2 + x   (:54)
-                            if (r == 2) { fin.a2 = 0.2f; fin.e2 = rin[i][q]; fin.s2 = 1.f; }           // out*0.2 + x (:70)
-                        }
-                        kloop(F, 0, ins, pan, fin, true, cw.b_off + 32 * q, nullptr);
-                    }
-                    if (c < 4) a.xs[c] = o; else a.out = o;
+                    (c < 4 ? a.xs[c] : a.out) = alloc_t(0);
+                    if (c < 4 && rdb_bits) a.xb[c] = reinterpret_cast<unsigned short*>(alloc_img(0, 1));
                 }
+                // Diagnostic (e->chunk): sweep the dense block in batch chunks -- with <= 1-2 images per sweep the block's six planes
+                // (6 x 33.5 MB per 512^2 image) stay in the Infinity Cache between conv_k and conv_{k+1..5}.
+                // `single`; needs P == 1: slice() cuts single-launch convs only
+                const int cb = (single && e->chunk > 0 && e->chunk < B) ? e->chunk : B;
+                for (int b0 = 0; b0 < B; b0 += cb)
+                    for (int c = 0; c < 5; ++c) {
+                        const ConvW& cw = e->rdb[(i * 3 + r) * 5 + c];
+                        const int ns = (c + 1) * P;
+                        std::vector<PlaneIn> ins;
+                        for (int t = 0; t <= c; ++t) for (float* pl : (t == 0 ? a.xin : a.xs[t - 1])) ins.push_back(std_in(pl, 0));
+                        for (int q = 0; q < P; ++q) {
+                            OutDesc fin = out_desc((c < 4 ? a.xs[c] : a.out)[q], 0);
+                            if (c < 4) { fin.slope = 0.2f; fin.bits_out = a.xb[c]; }                       // rrdb_blocks.py:38-52
+                            else {
+                                fin.a1 = 0.2f; fin.e1 = a.xin[q]; fin.s1 = 1.f;                            // x5*0.2 + x   (:54)
+                                if (r == 2) { fin.a2 = 0.2f; fin.e2 = rin[i][q]; fin.s2 = 1.f; }           // out*0.2 + x (:70)
+                            }
+                            kloop(F, 0, ins, panels(fwdp(cw.fwd_off), q, ns), fin, true, cw.b_off + 32 * q, nullptr, b0, std::min(cb, B - b0));
+                        }
+                    }
                 for (int k = 0; k < 4; ++k) release_t(a.xs[k], 0);
                 if (r > 0) release_t(a.xin, 0);
                 cur = a.out;
@@ -887,11 +651,9 @@ struct Builder {
         rin[blocks] = cur;
         Tensor T = alloc_t(0);
         for (int q = 0; q < P; ++q) { // fea + trunk_conv(rrdb(fea)) (generator_rrdb.py:68-69)
-            std::vector<const float*> pan;
-            for (int k = 0; k < P; ++k) pan.push_back(fwdp(e->trunk.fwd_off + ((long long)q * P + k) * PANEL_FLOATS));
             OutDesc fin = out_desc(T[q], 0);
             fin.e1 = fea[q]; fin.s1 = 1.f;
-            kloop(F, 0, planes_of(cur, 0), pan, fin, true, e->trunk.b_off + 32 * q, nullptr);
+            kloop(F, 0, planes_of(cur, 0), panels(fwdp(e->trunk.fwd_off), q, P), fin, true, e->trunk.b_off + 32 * q, nullptr);
         }
         release_t(cur, 0);
         release_t(fea, 0);
@@ -903,26 +665,30 @@ struct Builder {
             Tensor feat = T;
             for (int u = 0; u < nup; ++u) { // upsampling: conv 32P -> 128P, LeakyReLU(0.01), PixelShuffle(2) (generator_rrdb.py:93-99)
                 U[u] = alloc_t(u + 1);
-                for (int q = 0; q < P; ++q)
+                if (single) {   // the four sub-pixel chunks as ONE 4-output launch that publishes one maximum (alias_shuffled); needs P == 1: one input plane
+                    ConvParams p = conv_base(u);
+                    p.n_in = 1; p.n_out = 4; p.in[0] = std_in(feat[0], u); p.wpanel = fwdp(e->up[u].fwd_off);
+                    for (int n = 0; n < 4; ++n) { shuf_out(p.out[n], U[u][0], u, n); p.out[n].slope = 0.01f; }
+                    p.bias = e->pk_sbias + e->up[u].sbias_off;
+                    F.push_back(conv_launch(p, false, 0));
+                    alias_shuffled(U[u][0], u);
+                }
+                else for (int q = 0; q < P; ++q)
                     for (int sub = 0; sub < 4; ++sub) {           // chunk n = sub * P + q holds the channels 4 (32 q + c) + sub
                         const int n = sub * P + q;
-                        std::vector<const float*> pan;
-                        for (int k = 0; k < P; ++k) pan.push_back(fwdp(e->up[u].fwd_off + ((long long)n * P + k) * PANEL_FLOATS));
                         OutDesc fin = conv_base(u).out[0];
                         shuf_out(fin, U[u][q], u, sub);
                         fin.slope = 0.01f;
-                        kloop(F, u, planes_of(feat, u), pan, fin, false, 0, e->pk_sbias + e->up[u].sbias_off + 32 * n);
+                        kloop(F, u, planes_of(feat, u), panels(fwdp(e->up[u].fwd_off), n, P), fin, false, 0, e->pk_sbias + e->up[u].sbias_off + 32 * n);
                     }
                 release_t(feat, u);
                 feat = U[u];
             }
             H1 = alloc_t(lo);
             for (int q = 0; q < P; ++q) { // lrelu(HRconv(fea)) (generator_rrdb.py:107)
-                std::vector<const float*> pan;
-                for (int k = 0; k < P; ++k) pan.push_back(fwdp(e->hr.fwd_off + ((long long)q * P + k) * PANEL_FLOATS));
                 OutDesc fin = out_desc(H1[q], lo);
                 fin.slope = 0.2f;
-                kloop(F, lo, planes_of(feat, lo), pan, fin, true, e->hr.b_off + 32 * q, nullptr);
+                kloop(F, lo, planes_of(feat, lo), panels(fwdp(e->hr.fwd_off), q, P), fin, true, e->hr.b_off + 32 * q, nullptr);
             }
             release_t(feat, lo);
         }
@@ -963,33 +729,24 @@ struct Builder {
                     p.partial = eng->edge_partial; return run_edge_wgrad(eng, p, 1, eng->b_grads + wo, eng->b_grads + bo, s);
                 });
             }
-            if (!sr) {
-                for (int q = 0; q < P; ++q)
-                    for (int co = 0; co < CO; ++co) {
-                        EdgeExpandParams p; memset(&p, 0, sizeof(p));
-                        p.B = B; p.H = H; p.W = W; p.s = dpre + co * HWo; p.s_bs = CO * HWo; p.w = last_bwd(co, q); p.out = dT[q]; p.mslope = 1.f;
-                        p.accumulate = co > 0;
-                        S.push_back([eng, p](hipStream_t s) { return run_edge_expand(eng, p, s); });
-                    }
-            } else {
-                Tensor GH = alloc_t(lo);
-                for (int q = 0; q < P; ++q)   // d(H1) masked by lrelu'(0.2): the output channels' contributions summed, the mask on the last
-                    for (int co = 0; co < CO; ++co) {
-                        EdgeExpandParams p; memset(&p, 0, sizeof(p));
-                        p.B = B; p.H = H << lo; p.W = W << lo; p.s = dpre + co * HWo; p.s_bs = CO * HWo; p.w = last_bwd(co, q); p.out = GH[q];
-                        p.accumulate = co > 0; p.mslope = 1.f;
-                        if (co == CO - 1) { p.mask = H1[q]; p.mslope = 0.2f; }
-                        S.push_back([eng, p](hipStream_t s) { return run_edge_expand(eng, p, s); });
-                    }
+            Tensor GH = sr ? alloc_t(lo) : dT;      // conv_last's input gradient: DN d(T); SR d(H1) masked by lrelu'(0.2)
+            for (int q = 0; q < P; ++q)   // the output channels' contributions summed, the mask on the last
+                for (int co = 0; co < CO; ++co) {
+                    EdgeExpandParams p; memset(&p, 0, sizeof(p));
+                    p.B = B; p.H = H << lo; p.W = W << lo; p.s = dpre + co * HWo; p.s_bs = CO * HWo; p.w = last_bwd(co, q); p.out = GH[q];
+                    p.accumulate = co > 0; p.mslope = 1.f;
+                    if (sr && co == CO - 1) { p.mask = H1[q]; p.mslope = 0.2f; }
+                    if (single) p.amax = report_slot(GH[q], lo);      // needs CO == 1: no `amax` with `accumulate`, as on conv_first
+                    S.push_back([eng, p](hipStream_t s) { return run_edge_expand(eng, p, s); });
+                }
+            if (sr) {
                 const Tensor& hr_in = nup > 0 ? U[nup - 1] : T;
                 wgrad_all(S, lo, planes_of(hr_in, lo), GH, e->hr, 1.f);
                 Tensor G = nup > 0 ? alloc_t(lo) : dT;
                 for (int pl = 0; pl < P; ++pl) { // HRconv input gradient (masked by the upsample LeakyReLU(0.01) when it feeds a pixel-shuffle)
-                    std::vector<const float*> pan;
-                    for (int k = 0; k < P; ++k) pan.push_back(bwdp(e->hr.bwd_off + ((long long)pl * P + k) * PANEL_FLOATS));
                     OutDesc fin = out_desc(G[pl], lo);
                     if (nup > 0) { fin.mask = U[nup - 1][pl]; fin.mslope = 0.01f; }
-                    kloop(S, lo, planes_of(GH, lo), pan, fin, false, 0, nullptr);
+                    kloop(S, lo, planes_of(GH, lo), panels(bwdp(e->hr.bwd_off), pl, P), fin, false, 0, nullptr);
                 }
                 for (int u = nup - 1; u >= 0; --u) {
                     const Tensor& xin = u > 0 ? U[u - 1] : T;
@@ -1000,16 +757,12 @@ struct Builder {
                     }
                     Tensor Gn = u > 0 ? alloc_t(u) : dT;
                     for (int pl = 0; pl < P; ++pl) {
-                        std::vector<PlaneIn> ins;
-                        std::vector<const float*> pan;
+                        std::vector<PlaneIn> ins;      // chunk sub * P + q of the shuffle conv's output, in panel order
                         for (int sub = 0; sub < 4; ++sub)
-                            for (int q = 0; q < P; ++q) {
-                                ins.push_back(shuf_in(G[q], u, sub));
-                                pan.push_back(bwdp(e->up[u].bwd_off + ((long long)pl * (4 * P) + (sub * P + q)) * PANEL_FLOATS));
-                            }
+                            for (int q = 0; q < P; ++q) ins.push_back(shuf_in(G[q], u, sub));
                         OutDesc fin = out_desc(Gn[pl], u);
                         if (u > 0) { fin.mask = U[u - 1][pl]; fin.mslope = 0.01f; }
-                        kloop(S, u, ins, pan, fin, false, 0, nullptr);
+                        kloop(S, u, ins, panels(bwdp(e->up[u].bwd_off), pl, 4 * P), fin, false, 0, nullptr);
                     }
                     G = Gn;
                 }
@@ -1018,27 +771,39 @@ struct Builder {
             wgrad_all(S, 0, planes_of(rin[blocks], 0), dT, e->trunk, 1.f);
         }
         Tensor dR = alloc_t(0);
-        for (int pl = 0; pl < P; ++pl) {
-            std::vector<const float*> pan;
-            for (int k = 0; k < P; ++k) pan.push_back(bwdp(e->trunk.bwd_off + ((long long)pl * P + k) * PANEL_FLOATS));
-            kloop(e->bwd_stages[0], 0, planes_of(dT, 0), pan, out_desc(dR[pl], 0), false, 0, nullptr);
-        }
+        for (int pl = 0; pl < P; ++pl)
+            kloop(e->bwd_stages[0], 0, planes_of(dT, 0), panels(bwdp(e->trunk.bwd_off), pl, P), out_desc(dR[pl], 0), false, 0, nullptr);
         Tensor dS[5] = {Tensor(), alloc_t(0), alloc_t(0), alloc_t(0), alloc_t(0)};
         for (int i = blocks - 1; i >= 0; --i) {
             std::vector<Launch>& S = e->bwd_stages[blocks - i];
             Tensor dOut = dR;
             for (int r = 2; r >= 0; --r) {
-                const RdbActM& a = acts[i * 3 + r];
+                const RdbAct& a = acts[i * 3 + r];
                 const float gscale = r == 2 ? 0.04f : 0.2f;
                 const ConvW* cw = &e->rdb[(i * 3 + r) * 5];
                 dS[0] = alloc_t(0);
                 const Tensor* xpl[5] = {&a.xin, &a.xs[0], &a.xs[1], &a.xs[2], &a.xs[3]};
-                // as in build(): dS_j = sum_{c>j} conv^T_c[j](G_c) as ONE K-loop over the planes of G_5 = dOut, G_4 .. G_{j+1}
+                // Input-gradients as K-loops (no read-modify-write): dS_j = sum_{c>j} conv^T_c[j](G_c) in ONE K-loop over
+                // the planes of G_5 = dOut, G_4..G_{j+1}; its epilogue adds the residual-path terms (j = 0) or applies
+                // lrelu'(x_j) (j >= 1), which makes dS_j the G_j of conv_j.  conv5's 0.2 / 0.04 factor lives in its
+                // transposed panels (PackDesc.bwd_scale); its weight gradient uses the unscaled dOut and scales in the reduce.
                 const Tensor* Gp[6] = {nullptr, &dS[1], &dS[2], &dS[3], &dS[4], &dOut}; // G_c, c = 1..5
+                // one pair-list weight-gradient launch per dense block (f16x3 kernel) once every G exists, i.e. in front of dS_0
+                // (XSD_WGRAD_BLOCK=0 restores one launch per G for same-library A/Bs: 122.6 -> 125.6 tiles/s on one device, profiles/r04_ab_wgrad_block_launch.txt)
+#ifdef XSD_TEST_HOOKS
+                static const bool block_wgrad = getenv("XSD_WGRAD_BLOCK") ? atoi(getenv("XSD_WGRAD_BLOCK")) != 0 : true;
+#else
+                constexpr bool block_wgrad = true;
+#endif
+                // `single`; needs P == 1: the pair list is the fifteen (X, G) pairs of one-plane tensors.  Both role-split weight-gradient
+                // kernels take pair lists; fewer than 120 CUs: one launch per G
+                const bool mega = single && block_wgrad && e->math >= 3 && block_parts_per_xcd(e->ncu) >= 1;
                 for (int c = 4; c >= 0; --c) { // conv index c (0-based) = conv_{c+1}
                     std::vector<PlaneIn> xs;
                     for (int t = 0; t <= c; ++t) for (float* pl : *xpl[t]) xs.push_back(std_in(pl, 0));
-                    wgrad_all(S, 0, xs, *Gp[c + 1], cw[c], c == 4 ? gscale : 1.f);
+                    if (!mega) wgrad_all(S, 0, xs, *Gp[c + 1], cw[c], c == 4 ? gscale : 1.f);
+                    else if (c == 0) wgrad_block_launch(S, xpl, Gp, cw, gscale);
+                    // now every G needed by dS_c exists: G_5 .. G_{c+1}
                     const int j = c;
                     for (int pl = 0; pl < P; ++pl) {
                         std::vector<PlaneIn> ins;
@@ -1054,7 +819,7 @@ struct Builder {
                         if (j == 0) {
                             fin.e1 = dOut[pl]; fin.s1 = r == 2 ? 0.2f : 1.f;
                             if (r == 0) { fin.e2 = dR[pl]; fin.s2 = 1.f; if (i == 0) { fin.e3 = dT[pl]; fin.s3 = 1.f; } }
-                        } else { fin.mask = (*xpl[j])[pl]; fin.mslope = 0.2f; }
+                        } else { fin.mask = (*xpl[j])[pl]; fin.mslope = 0.2f; fin.bits_in = a.xb[j - 1]; }
                         kloop(S, 0, ins, pan, fin, false, 0, nullptr);
                     }
                 }
