@@ -250,7 +250,8 @@ int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, in
  * The reference's SwinFIR (models/transformer/swinfir.py:120-441 with the Swin blocks of modules.py; factory models/model.py:187-200,
  * XMM configuration res/configs/models.toml [swinfir]: img_size 416, patch_size 32, window_size 16 -> an effective window of 13 without
  * shift, embed_dim 180, 6 x 6 blocks of 6 heads, in_chans 1, upscale 2).  Eval-mode forward in exact fp32: the linear layers, the
- * window attention and the 3x3 convs on the fp32 MFMA, the FourierUnit's FFTs on the vector ALUs; xsd_set_math does not apply.  No
+ * window attention and the 3x3 convs on the fp32 MFMA, the FourierUnit's FFTs on the vector ALUs.  xsd_set_math and XSD_MATH do not
+ * apply; xsd_swinfir_set_math below switches the linear layers and the 3x3 convs (nothing else) to the strict bf16x6 split.  No
  * float atomics: outputs are bitwise reproducible and each image's output is independent of the batch it is computed in.
  * Flat parameter layout: fp32, the order of SwinFIR.parameters() (conv_first.*, patch_embed.norm.* (patch_norm), per layer i and
  * block j layers.i.residual_group.blocks.j.{norm1.*, attn.relative_position_bias_table, attn.qkv.weight[, .bias], attn.proj.*, norm2.*,
@@ -288,17 +289,38 @@ int xsd_swinfir_pack_weights(xsd_swinfir* r, const float* dev_params, void* stre
  * x: [B][in_chans][H][W], y: [B][in_chans][upscale H][upscale W]; H and W multiples of the effective window and, with SFB, FFT sizes
  * (<= 4096, prime factors <= 13).  A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
 int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* Math mode of the engine's GEMMs -- every Linear, 1x1 and 3x3 conv of the forward (csrc/sw_gemm_s3x.h) -- in the mode numbers of
+ * xsd_set_math: 0 = "fp32" (default; these engines do not read XSD_MATH) and 3 = "bf16x6": both operands split exactly into three bf16
+ * terms, the six products hh, hm, mh, hl, lh, mm on v_mfma_f32_32x32x16_bf16, fp32 accumulation (hh apart from the five small ones).
+ * Window attention, LayerNorm and the FFT stay exact fp32 in every mode.  4 ("f16x3") is refused with XSD_ERR_ARG: its fp16 terms need
+ * a per-tensor scale that these kernels do not publish; any other number is refused with the list of modes.  May be called at any
+ * time and in any order: the mode holds from the next forward, and nothing but the usual xsd_swinfir_pack_weights is asked of the
+ * caller (the bf16 planes of the weights are made from dev_params at the first forward after a pack or a switch to bf16x6, so
+ * dev_params must still hold what was packed).  nparams and the flat layout do not depend on the mode.  Outputs stay bitwise
+ * reproducible and independent of the batch.  One limit of bf16x6: an fp32 value above bf16's largest finite value (3.39e38)
+ * splits to inf, which makes the output of ITS image non-finite. */
+int xsd_swinfir_set_math(xsd_swinfir* r, int mode);
+int xsd_swinfir_get_math(const xsd_swinfir* r);
 /* 1 if the FourierUnit's FFT takes a length of n, else 0 */
 int xsd_swinfir_fft_supported(int n);
 /* the FourierUnit's transform pair on its own: x [B][H][W][C2] (token-major real) -> spec [B][H][W/2+1][2 C2] (re, im interleaved)
  * = rfftn(x, norm="ortho"); with inverse set, x += irfftn(spec, s=(H, W), norm="ortho") and spec is overwritten. */
 int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, int H, int W, int C2, int inverse, void* stream);
 
+/* The GEMM that SwinFIR and HAT share, on its own (tests): y = act(A W^T + bias), written token-major with a row pitch of ldy >= N floats
+ * (only the B H W x N results are written).  conv3 = 0: A is [B H W][cin] token rows and dev_w [N][cin] as a Linear stores it;
+ * conv3 = 1: A is a token-major image [B][H W][cin], dev_w [N][cin][3][3] as a Conv2d stores it, zero padding 1.  The call packs the
+ * weights itself.  dev_bias [N] or NULL; act 0 none, 1 GELU (exact erf), 2 LeakyReLU(slope); math 0 (fp32) or 3 (bf16x6).  Synchronises
+ * the stream. */
+int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int conv3, int B, int H, int W, int cin,
+                     int N, int64_t ldy, int act, float slope, int math, void* stream);
+
 /* ---- HAT super-resolution, forward only (csrc/hat.hip) ------------------------------------------------------
  * The reference's HAT (models/transformer/hat.py:10-913; factory models/model.py:216-229, XMM configuration res/configs/models.toml
  * [hat]: img_size 416, patch_size 16, window_size 16, embed_dim 180, 6 groups of 6 HABs + 1 OCAB with 6 heads, in_chans 1, upscale 2,
  * overlap_ratio 0.5 -> 24 x 24 keys per 16 x 16 window).  Eval-mode forward in exact fp32 on SwinFIR's kernels (GEMM / conv3x3, window
- * attention, LayerNorm) plus the overlapping cross-attention, the channel attention and the HAB combine; xsd_set_math does not apply.
+ * attention, LayerNorm) plus the overlapping cross-attention, the channel attention and the HAB combine.  xsd_set_math and XSD_MATH do
+ * not apply; xsd_hat_set_math below switches the linear layers and the 3x3 convs (nothing else) to the strict bf16x6 split.
  * No float atomics: outputs are bitwise reproducible and each image's output is independent of the batch it is computed in.
  * Flat parameter layout: fp32, the order of HAT.parameters() (conv_first.*, patch_embed.norm.* (patch_norm), per layer i:
  * layers.i.residual_group.blocks.j.{norm1.*, attn.relative_position_bias_table, attn.qkv.weight[, .bias], attn.proj.*,
@@ -343,6 +365,11 @@ int xsd_hat_pack_weights(xsd_hat* r, const float* dev_params, void* stream);
  * x: [B][in_chans][H][W], y: [B][in_chans][upscale H][upscale W]; H and W multiples of window_size (the reference does not pad).
  * A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
 int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* Math mode of the engine's GEMMs (linear layers, CAB convs, conv_first, the group convs, the upsampling tail): exactly
+ * xsd_swinfir_set_math above.  The window attention, the overlapping cross-attention, LayerNorm and the channel attention stay exact
+ * fp32 in every mode. */
+int xsd_hat_set_math(xsd_hat* r, int mode);
+int xsd_hat_get_math(const xsd_hat* r);
 /* the OCAB's attention on its own (hat.py:334-391 between the qkv Linear and proj): qkv [B][H W][3 C] token rows, table
  * [(ws + ow - 1)^2][heads] -> out [B][H W][C]; ws <= 16, ws <= ow <= 32, ow - ws even. */
 int xsd_hat_test_ocab(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int ow,

@@ -5,7 +5,8 @@
 // of the HABs, the LayerNorm and the weight packing are the kernels HAT shares with SwinFIR (sw_kernels.h), as is the host code of the
 // head, the MLP half block and the tail; this file adds what HAT has on top of them.  The same rules hold: every product an fp32 FMA,
 // sums over K and all statistics carried in double, no float atomics, every reduction in a fixed order, so an image's output is
-// bitwise independent of the batch it shares and of the run, and a NaN stays in its image.
+// bitwise independent of the batch it shares and of the run, and a NaN stays in its image.  The opt-in math mode bf16x6 (xsd_hat_set_math)
+// runs the GEMMs on sw_gemm_s3x.h's kernel instead; everything in this file stays exact fp32 in both modes.
 //
 // Kernels:
 //   hat_ocab_kernel          the overlapping cross-attention of an OCAB (hat.py:326-391), one workgroup per (window, head): the ws^2
@@ -20,6 +21,7 @@
 //                            conv1x1 -> ReLU -> conv1x1 -> Sigmoid (hat.py:21-24)
 //   hat_combine_kernel       x += (t * y[b, c]) * conv_scale (hat.py:29, :268), and with y null the plain x += t of the "identity" branches
 #include "sw_kernels.h"
+#include "sw_gemm_s3x.h"
 
 namespace {
 
@@ -436,6 +438,10 @@ int xsd_hat_pack_weights(xsd_hat* r, const float* dev_params, void* stream)
     return pack_weights(r, "HAT", dev_params, stream);
 }
 
+int xsd_hat_set_math(xsd_hat* r, int mode) { return set_math(r, "HAT", mode); }
+
+int xsd_hat_get_math(const xsd_hat* r) { return r ? r->math : -1; }
+
 int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream)
 {
     if (!r || !dev_x || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
@@ -447,6 +453,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
     const long long up = r->cfg.upscale;
     if ((long long)H * W * up * up > (1ll << 28)) return rfail(XSD_ERR_ARG, "HAT: image of %d x %d pixels is too large", H, W);
     if (!r->packed) return rfail(XSD_ERR_STATE, "xsd_hat_pack_weights must be called before xsd_hat_forward");
+    if (int rc = ready_math(r, "HAT", (hipStream_t)stream)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (r->B != B || r->H != H || r->W != W) {
         int rc = grow_ws(r, "HAT", plan_ws(r, B, H, W, false), B, H, W);
@@ -473,12 +480,12 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             // HAB (hat.py:220-271): x = x + proj(attn(u)) + conv_scale * CAB(u), u = norm1(x); then the MLP
             HT(ln(s, X, O, PP(r, k.n1w), PP(r, k.n1b), M, E));
             GemmP p = gp_tok(O, M, E, E, wt + k.qkv.t, 3 * E, PP(r, k.qkv.b), r->A, 3 * E);
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             p = gp_conv(O, B, H, W, E, wt + k.c1.t, r->Cc, PP(r, k.c1.b), r->T1, r->Cc);       // CAB (hat.py:36-41)
             p.act = ACT_GELU;
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             p = gp_conv(r->T1, B, H, W, r->Cc, wt + k.c2.t, E, PP(r, k.c2.b), r->T2, E);
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             HT(pool_partial(s, r->T2, PART, B, HW, E));
             hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(E + r->Cs), s, PART, nchunk, HW, E, r->Cs,
                                r->params + k.sq1.w, r->params + k.sq1.b, r->params + k.sq2.w, r->params + k.sq2.b, (float*)nullptr, r->YC);
@@ -487,7 +494,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             HT(attention(s, r->A, O, r->params + k.table, B, H, W, E, L.heads, r->ws, k.shift, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
             p.res = X; p.rbs = 0; p.rps = E;
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             HT(combine(s, X, r->T2, r->YC, (float)c.conv_scale, B, HW, E));
             HT(mlp(s, r, X, O, M, k.n2w, k.n2b, k.fc1, k.fc2));                              // hat.py:269
         }
@@ -495,17 +502,17 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             const OBlk& o = L.oca;
             HT(ln(s, X, O, PP(r, o.n1w), PP(r, o.n1b), M, E));
             GemmP p = gp_tok(O, M, E, E, wt + o.qkv.t, 3 * E, PP(r, o.qkv.b), r->A, 3 * E);
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             HT(ocab(s, r->A, O, r->params + o.table, B, H, W, E, L.heads, r->ws, r->ow, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + o.proj.t, E, PP(r, o.proj.b), X, E);
             p.res = X; p.rbs = 0; p.rps = E;
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             HT(mlp(s, r, X, O, M, o.n2w, o.n2b, o.fc1, o.fc2));                              // hat.py:395
         }
         if (c.resi_connection == 0) {
             GemmP p = gp_conv(X, B, H, W, E, wt + L.conv.t, E, PP(r, L.conv.b), O, E);
             p.res = r->R0; p.rbs = HW * E; p.rps = E;
-            HT(gemm(s, p));
+            HT(gemm(s, r, p));
             std::swap(X, O);
         } else {
             HT(combine(s, X, r->R0, nullptr, 1.f, B, HW, E));
@@ -516,7 +523,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
     if (c.resi_connection == 0) {
         GemmP p = gp_conv(O, B, H, W, E, wt + r->after.t, E, PP(r, r->after.b), X, E);
         p.res = XF; p.rbs = HW * E; p.rps = E;
-        HT(gemm(s, p));
+        HT(gemm(s, r, p));
     } else {
         HT(combine(s, O, XF, nullptr, 1.f, B, HW, E));
         std::swap(X, O);

@@ -18,6 +18,8 @@
 //                    norm), one wave per token, statistics in double.
 //   sw_pack_kernel   a Linear / conv weight as stored -> the [K][N] matrix sw_gemm_kernel reads.
 //
+// The opt-in bf16x6 math mode runs the GEMM on sw_gemm_s3x.h's kernel instead; everything here stays exact fp32 in every mode.
+//
 // Everything is in an anonymous namespace: each including file compiles its own instance.
 #ifndef XSD_SW_KERNELS_H
 #define XSD_SW_KERNELS_H
@@ -333,7 +335,7 @@ __global__ __launch_bounds__(256) void sw_pack_kernel(const float* src, float* d
     dst[i] = src[((long long)co * cin + ci) * taps + t];
 }
 
-struct Lin { long long w = -1, b = -1, t = -1; int cout = 0, cin = 0, taps = 1; };   // flat offsets of weight / bias, packed copy
+struct Lin { long long w = -1, b = -1, t = -1, t3 = -1; int cout = 0, cin = 0, taps = 1; };   // flat offsets of weight / bias, packed copy, bf16x6 planes
 
 long long add(long long& off, long long n) { const long long o = off; off += n; return o; }
 
@@ -394,6 +396,9 @@ struct SwBase {
     std::vector<Lin> ups;
     std::vector<Lin*> lins;           // every weight the GEMM reads, in the order of the packed copy
     float* wt = nullptr;              // the packed copy
+    int math = 0;                     // 0 = fp32, 3 = bf16x6 (sw_gemm_s3x.h): which kernel the forward's GEMMs run on
+    unsigned short* wt3 = nullptr;    // bf16x6: the three bf16 planes of every weight, allocated when the mode is first used
+    bool packed3 = false;             // wt3 follows the last pack_weights
     float* mean = nullptr;
     const float* params = nullptr;
     bool packed = false;
@@ -408,10 +413,14 @@ struct SwBase {
     ~SwBase()
     {
         if (wt) hipFree(wt);
+        if (wt3) hipFree(wt3);
         if (mean) hipFree(mean);
         if (ws_buf) hipFree(ws_buf);
     }
 };
+
+// the GEMM in the engine's math mode (sw_gemm_s3x.h); every GEMM of a forward goes through it
+hipError_t gemm(hipStream_t s, const SwBase* r, const GemmP& p);
 
 const float* PP(const SwBase* r, long long off) { return off < 0 ? nullptr : r->params + off; }
 
@@ -475,6 +484,7 @@ int pack_weights(SwBase* r, const char* net, const float* dev_params, void* stre
         if (e) return rfail(XSD_ERR_HIP, "%s weight packing: %s", net, hipGetErrorString(e));
     }
     r->packed = true;
+    r->packed3 = false;               // the bf16x6 planes are made again before the next forward that needs them
     return XSD_OK;
 }
 
@@ -530,7 +540,7 @@ hipError_t head(hipStream_t s, const SwBase* r, const float* dev_x, int in_chans
     GemmP p = gp_conv(dev_x, r->B, r->H, r->W, in_chans, r->wt + r->first_l.t, r->E, PP(r, r->first_l.b), r->XF, r->E);
     p.acs = HW; p.aps = 1;
     p.isub = r->mean; p.imul = img_range;
-    hipError_t e = gemm(s, p);
+    hipError_t e = gemm(s, r, p);
     if (e) return e;
     if (patch_norm) return ln(s, r->XF, r->X, PP(r, r->pen_w), PP(r, r->pen_b), M, r->E);
     return hipMemcpyAsync(r->X, r->XF, sizeof(float) * M * r->E, hipMemcpyDeviceToDevice, s);
@@ -544,10 +554,10 @@ hipError_t mlp(hipStream_t s, const SwBase* r, float* X, float* O, long long M, 
     if (e) return e;
     GemmP p = gp_tok(O, M, E, E, r->wt + fc1.t, r->hid, PP(r, fc1.b), r->A, r->hid);
     p.act = ACT_GELU;
-    if ((e = gemm(s, p))) return e;
+    if ((e = gemm(s, r, p))) return e;
     p = gp_tok(r->A, M, r->hid, r->hid, r->wt + fc2.t, E, PP(r, fc2.b), X, E);
     p.res = X; p.rbs = 0; p.rps = E;
-    return gemm(s, p);
+    return gemm(s, r, p);
 }
 
 // conv_before_upsample + LeakyReLU(0.01), the PixelShuffle stages of Upsample, conv_last into NCHW x / img_range + mean
@@ -556,7 +566,7 @@ hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, in
     const int B = r->B, nf = r->nfeat;
     GemmP p = gp_conv(X, B, r->H, r->W, r->E, r->wt + r->before.t, nf, PP(r, r->before.b), r->V, nf);
     p.act = ACT_LRELU; p.slope = 0.01f;
-    hipError_t e = gemm(s, p);
+    hipError_t e = gemm(s, r, p);
     if (e) return e;
     const float* cur = r->V;
     int h = r->H, w = r->W;
@@ -565,12 +575,12 @@ hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, in
         float* dst = (i % 2 == 0) ? r->U0 : r->U1;
         p = gp_conv(cur, B, h, w, nf, r->wt + r->ups[i].t, f * f * nf, PP(r, r->ups[i].b), dst, nf);
         p.omode = O_SHUFFLE; p.r = f; p.ybs = (long long)h * w * f * f * nf; p.yps = nf;
-        if ((e = gemm(s, p))) return e;
+        if ((e = gemm(s, r, p))) return e;
         cur = dst; h *= f; w *= f;
     }
     p = gp_conv(cur, B, h, w, nf, r->wt + r->last.t, in_chans, PP(r, r->last.b), dev_y, 0);
     p.omode = O_NCHW; p.ybs = (long long)in_chans * h * w; p.omean = r->mean; p.orange = img_range;
-    return gemm(s, p);
+    return gemm(s, r, p);
 }
 
 } // namespace

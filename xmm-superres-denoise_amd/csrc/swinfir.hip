@@ -6,6 +6,8 @@
 // whose butterflies are fp32 FMAs on the vector ALUs in a fixed order, and the network.  The NHWC view of a token-major map is what
 // PatchUnEmbed / PatchEmbed (modules.py:423-500) turn into NCHW and back, so the convs of the SFB block, the head and the tail read
 // and write it through their addressing; only the network input and output are NCHW.
+// The opt-in math mode bf16x6 (xsd_swinfir_set_math) runs the GEMMs on sw_gemm_s3x.h's kernel instead; attention, LayerNorm and the
+// FFT stay exact fp32 in both modes.
 //
 // Kernels:
 //   sw_fft_kernel    one pass of the FourierUnit's 2-D transform (swinfir.py:14-61) over lines of one axis: R2C along W, complex
@@ -14,6 +16,7 @@
 //                    [B][H][W/2+1][2 c + re/im]: the channel order of the reference's stack / permute / view, so the 1x1 conv
 //                    over the spectrum is a plain token GEMM.
 #include "sw_kernels.h"
+#include "sw_gemm_s3x.h"
 
 namespace {
 
@@ -367,6 +370,10 @@ int xsd_swinfir_pack_weights(xsd_swinfir* r, const float* dev_params, void* stre
     return pack_weights(r, "SwinFIR", dev_params, stream);
 }
 
+int xsd_swinfir_set_math(xsd_swinfir* r, int mode) { return set_math(r, "SwinFIR", mode); }
+
+int xsd_swinfir_get_math(const xsd_swinfir* r) { return r ? r->math : -1; }
+
 int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream)
 {
     if (!r || !dev_x || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
@@ -381,6 +388,7 @@ int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B,
     const long long up = r->cfg.upscale;
     if ((long long)H * W * up * up > (1ll << 28)) return rfail(XSD_ERR_ARG, "SwinFIR: image of %d x %d pixels is too large", H, W);
     if (!r->packed) return rfail(XSD_ERR_STATE, "xsd_swinfir_pack_weights must be called before xsd_swinfir_forward");
+    if (int rc = ready_math(r, "SwinFIR", (hipStream_t)stream)) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (r->B != B || r->H != H || r->W != W) {
         int rc = grow_ws(r, "SwinFIR", plan_ws(r, B, H, W, false), B, H, W);
@@ -409,11 +417,11 @@ int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B,
             // norm1 into O (free until the attention writes it); a LayerNorm prologue inside the GEMM measured slower, DESIGN §12
             SW(ln(s, X, O, PP(r, k.n1w), PP(r, k.n1b), M, E));
             GemmP p = gp_tok(O, M, E, E, wt + k.qkv.t, 3 * E, PP(r, k.qkv.b), r->A, 3 * E);
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             SW(attention(s, r->A, O, r->params + k.table, B, H, W, E, L.heads, r->ws, k.shift, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
             p.res = X; p.rbs = 0; p.rps = E;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             SW(mlp(s, r, X, O, M, k.n2w, k.n2b, k.fc1, k.fc2));
         }
         if (c.resi_connection == 0) {
@@ -421,29 +429,29 @@ int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B,
             float* CAT = r->A;
             GemmP p = gp_conv(X, B, H, W, E, wt + L.s0.t, E, PP(r, L.s0.b), O, E);
             p.act = ACT_LRELU; p.slope = 0.2f;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             p = gp_conv(O, B, H, W, E, wt + L.s2.t, E, PP(r, L.s2.b), CAT, 2 * E);
             p.res = X; p.rbs = HW * E; p.rps = E;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             p = gp_tok(X, M, E, E, wt + L.c1.t, C2, PP(r, L.c1.b), r->Y1, C2);
             p.act = ACT_LRELU; p.slope = 0.2f;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             SW(fft(fs, s, F_R2C_ROWS, r->Y1, r->S1));
             SW(fft(fs, s, F_COLS_FWD, r->S1, r->S1));
             p = gp_tok(r->S1, Ms, 2 * C2, 2 * C2, wt + L.fu.t, 2 * C2, PP(r, L.fu.b), r->S2, 2 * C2);
             p.act = ACT_LRELU; p.slope = 0.2f;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             SW(fft(fs, s, F_COLS_INV, r->S2, r->S2));
             SW(fft(fs, s, F_C2R_ROWS, r->S2, r->Y1));                                             // Y1 = x + fu(x)
             p = gp_tok(r->Y1, M, C2, C2, wt + L.c2.t, E, PP(r, L.c2.b), CAT + E, 2 * E);
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             p = gp_tok(CAT, M, 2 * E, 2 * E, wt + L.fus.t, E, PP(r, L.fus.b), X, E);
             p.res = r->R0; p.rbs = 0; p.rps = E;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
         } else {
             GemmP p = gp_conv(X, B, H, W, E, wt + L.conv1.t, E, PP(r, L.conv1.b), O, E);
             p.res = r->R0; p.rbs = HW * E; p.rps = E;
-            SW(gemm(s, p));
+            SW(gemm(s, r, p));
             std::swap(X, O);
         }
     }
@@ -452,7 +460,7 @@ int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B,
     {
         GemmP p = gp_conv(O, B, H, W, E, wt + r->after.t, E, PP(r, r->after.b), X, E);
         p.res = XF; p.rbs = HW * E; p.rps = E;
-        SW(gemm(s, p));
+        SW(gemm(s, r, p));
     }
     SW(tail(s, r, X, dev_y, c.in_chans, c.upscale, (float)c.img_range));
 #undef SW
@@ -480,6 +488,12 @@ int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, i
     if (!e) e = inverse ? fft(fs, s, F_C2R_ROWS, dev_spec, dev_x) : fft(fs, s, F_COLS_FWD, dev_spec, dev_spec);
     if (e) return rfail(XSD_ERR_HIP, "SwinFIR FFT test: %s", hipGetErrorString(e));
     return XSD_OK;
+}
+
+int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int conv3, int B, int H, int W, int cin,
+                     int N, int64_t ldy, int act, float slope, int math, void* stream)
+{
+    return test_gemm(dev_a, dev_w, dev_bias, dev_y, conv3, B, H, W, cin, N, ldy, act, slope, math, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -127,6 +127,11 @@ def load():
     L.xsd_hat_param_count.restype = i64
     L.xsd_hat_pack_weights.argtypes = [vp, fp, vp]
     L.xsd_hat_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
+    L.xsd_swinfir_set_math.argtypes = [vp, i32]
+    L.xsd_swinfir_get_math.argtypes = [vp]
+    L.xsd_hat_set_math.argtypes = [vp, i32]
+    L.xsd_hat_get_math.argtypes = [vp]
+    L.xsd_sw_test_gemm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i64, i32, f32, i32, vp]
     L.xsd_hat_test_ocab.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     L.xsd_hat_test_channel_mean.argtypes = [fp, fp, i32, i64, i32, vp]
     _lib = L
@@ -141,9 +146,9 @@ ABI_SYMBOLS = [
     "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
-    "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft",
+    "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
     "xsd_hat_create", "xsd_hat_destroy", "xsd_hat_param_count", "xsd_hat_pack_weights", "xsd_hat_forward", "xsd_hat_test_ocab",
-    "xsd_hat_test_channel_mean",
+    "xsd_hat_test_channel_mean", "xsd_hat_set_math", "xsd_hat_get_math",
 ]
 
 

@@ -252,11 +252,39 @@ class _ForwardEngine:
         check(self._c("forward")(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
         return y
 
+    # ---- math mode of the GEMMs (include/xsd.h: xsd_swinfir_set_math / xsd_hat_set_math); the mode numbers of Engine.MATH
+    MATH = {"fp32": 0, "bf16x6": 3}
+    NAME = ""
+
+    def set_math(self, mode: str):
+        """'fp32' (default: exact fp32 MFMA) or 'bf16x6' (strict: exact 3-term bf16 split of both operands, 6 products, fp32
+        accumulation) for the linear layers and the 3x3 convs; attention, LayerNorm, FFT and channel attention stay exact fp32.
+        Takes effect at the next forward; no repack is needed."""
+        if mode == "f16x3":
+            raise XsdError(f"{self.NAME}: math mode 'f16x3' is not supported: its fp16 terms need a per-tensor scale that these kernels do "
+                           f"not publish; the modes are {sorted(self.MATH)}")
+        if mode not in self.MATH:
+            raise XsdError(f"{self.NAME}: unknown math mode {mode!r}: the modes are {sorted(self.MATH)}")
+        check(self._c("set_math")(self.h, self.MATH[mode]))
+
+    def get_math(self) -> str:
+        return {v: k for k, v in self.MATH.items()}[int(self._c("get_math")(self.h))]
+
 
 class RestormerEngine(_ForwardEngine):
     """One Restormer engine per module per GPU (xsd_restormer_create / _destroy): forward only."""
 
     PREFIX = "xsd_restormer_"
+    NAME = "Restormer"
+    MATH = {"fp32": 0}
+
+    def set_math(self, mode: str):
+        """Restormer's kernels are exact fp32 on the vector ALUs: 'fp32' is the only mode."""
+        if mode != "fp32":
+            raise XsdError(f"Restormer: math mode {mode!r} is not supported: the Restormer engine computes in 'fp32' only")
+
+    def get_math(self) -> str:
+        return "fp32"
 
     def __init__(self, inp_channels: int, out_channels: int, dim: int, num_blocks, num_refinement_blocks: int, heads,
                  ffn_expansion_factor: float, bias: bool, layernorm_bias_free: bool):
@@ -275,6 +303,7 @@ class SwinFIREngine(_ForwardEngine):
     UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
     RESI = ("SFB", "1conv", "HSFB", "identity")
     PREFIX = "xsd_swinfir_"
+    NAME = "SwinFIR"
 
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
                  qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
@@ -317,6 +346,7 @@ class HATEngine(_ForwardEngine):
     UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
     RESI = ("1conv", "identity")
     PREFIX = "xsd_hat_"
+    NAME = "HAT"
 
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, compress_ratio: int,
                  squeeze_factor: int, conv_scale: float, overlap_ratio: float, mlp_ratio: float, qkv_bias: bool, qk_scale, ape: bool,
@@ -351,6 +381,58 @@ def hat_ocab_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, h
     check(_lib.load().xsd_hat_test_ocab(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), B, H, W, C3 // 3, heads, ws, ow, float(scale),
                                         _stream_ptr(qkv.device)))
     return out
+
+
+SW_ACT = {None: 0, "gelu": 1, "lrelu": 2}
+SW_MATH = {"fp32": 0, "bf16x6": 3}
+
+
+def _sw_test_gemm(a, w, bias, act, math, conv3, B, H, W, cin, out):
+    _require_cuda_f32(a, "a")
+    _require_cuda_f32(w, "w")
+    if act not in SW_ACT:
+        raise XsdError(f"unknown activation {act!r}: {list(SW_ACT)}")
+    if math not in SW_MATH:
+        raise XsdError(f"unknown math mode {math!r}: the modes are {sorted(SW_MATH)}")
+    N = int(w.shape[0])
+    if bias is not None:
+        _require_cuda_f32(bias, "bias")
+        if bias.numel() != N:
+            raise XsdError(f"bias has {bias.numel()} elements for {N} outputs")
+    rows = B * H * W
+    if out is None:
+        out = torch.empty((rows, N), device=a.device, dtype=torch.float32)
+    else:
+        _require_cuda_f32(out, "out")
+        if out.dim() != 2 or out.shape[0] < rows or out.shape[1] < N:
+            raise XsdError(f"out {tuple(out.shape)} does not hold {rows} x {N}")
+    check(_lib.load().xsd_sw_test_gemm(a.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, out.data_ptr(),
+                                       int(conv3), B, H, W, cin, N, int(out.shape[1]), SW_ACT[act], 0.01, SW_MATH[math],
+                                       _stream_ptr(a.device)))
+    return out
+
+
+@_on_tensor_device
+def sw_gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, act: str | None = None, math: str = "fp32",
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """The GEMM of the SwinFIR / HAT engines on its own (include/xsd.h: xsd_sw_test_gemm): a [M, K] token rows, w [N, K] as a Linear
+    stores it -> act(a w^T + bias) [M, N]; act None, "gelu" (exact erf) or "lrelu" (slope 0.01); math "fp32" or "bf16x6".  With `out`
+    (2-D, at least M x N, contiguous) the result goes into its first M rows and N columns and nothing else of it is written."""
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1]:
+        raise XsdError(f"a {tuple(a.shape)} and w {tuple(w.shape)} are not [M, K] and [N, K]")
+    return _sw_test_gemm(a, w, bias, act, math, False, 1, 1, int(a.shape[0]), int(a.shape[1]), out)
+
+
+@_on_tensor_device
+def sw_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, math: str = "fp32", act: str | None = None,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """The same GEMM as the implicit im2col of a 3x3 conv (zero padding 1): x [B, H, W, cin] token-major, w [N, cin, 3, 3] as a Conv2d
+    stores it -> [B, H, W, N] token-major (with `out`: as sw_gemm, rows = B H W)."""
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[3], 3, 3):
+        raise XsdError(f"x {tuple(x.shape)} and w {tuple(w.shape)} are not [B, H, W, cin] and [N, cin, 3, 3]")
+    B, H, W, cin = (int(v) for v in x.shape)
+    y = _sw_test_gemm(x, w, bias, act, math, True, B, H, W, cin, out)
+    return y if out is not None else y.view(B, H, W, -1)
 
 
 @_on_tensor_device

@@ -228,6 +228,21 @@ class SwinFIR(FlatParams, nn.Module):
         self._flat = None
         self._plist = None
         self._packed_key = None
+        self._math = None  # None: the engine's default (fp32)
+
+    def set_math(self, mode: str):
+        """Math mode of the linear layers and 3x3 convs (SwinFIREngine.set_math): 'fp32' (exact, the default) or 'bf16x6' (strict split).  Kept
+        until an engine exists, applied again to the engine a device move creates, and carried by copies and pickles."""
+        if mode not in SwinFIREngine.MATH:
+            raise ValueError(f"SwinFIR: math mode {mode!r} is not supported; the modes are {sorted(SwinFIREngine.MATH)}"
+                             + (" (the fp16 terms of 'f16x3' need a per-tensor scale that these kernels do not publish)" if mode == "f16x3" else ""))
+        self._math = mode
+        if self._engine is not None:
+            self._engine.set_math(mode)
+        return self
+
+    def get_math(self) -> str:
+        return getattr(self, "_math", None) or "fp32"
 
     def __getstate__(self):
         st = super().__getstate__()
@@ -247,6 +262,8 @@ class SwinFIR(FlatParams, nn.Module):
                                              self.upscale, self.img_range, self.upsampler, self.resi_connection)
             self._engine_dev = flat.device
             self._packed_key = None
+            if getattr(self, "_math", None) is not None:
+                self._engine.set_math(self._math)
         return self._engine
 
     def _pack_if_changed(self):

@@ -269,14 +269,14 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
          dataset_type: str = "sim", lr_res: int = 416, lr_exps=(20,), hr_exp: int = 100, lr_det_mask=None, hr_det_mask=None,
          agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False, scaling: str = "linear", batch_size: int = 4, loss: str = "l1",
          seed: int | None = None, splits: str | None = None, device: str | None = None, max_pool_bytes: int | None = None,
-         log: bool = True, extended_metrics: bool = False) -> dict:
+         log: bool = True, extended_metrics: bool = False, math: str | None = None) -> dict:
     """The reference's `train.py test` (train.py:91-103,165-171) on one device: the test split of the dataset through the model
     of `checkpoint` (any model infer.load_model loads), returning the `test/...` values (loss, get_metrics, get_in_metrics).
     The split file must be the one `fit` wrote (default location: next to the checkpoint); `seed` defaults to the one recorded
     there, so the test samples draw the same realisations, AGN and backgrounds as fit's test epoch.  Without `extended_metrics` the
     extended piq / VIF collection is not computed and the routine says so (EXT_METRICS_NOTICE) instead of leaving it out silently; with
     it, get_ext_metrics / get_in_ext_metrics (vif_p, gmsd, ms_gmsd, haarpsi, msdi) are added and the notice names fsim as the one
-    metric left out."""
+    metric left out.  `math` is infer.load_model's: the math mode of the network (None: its default)."""
     from xmm_superres_denoise.data.datamodule import XmmDataModule
     from xmm_superres_denoise.infer import load_model
     from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
@@ -294,7 +294,7 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
         with open(splits) as f:
             seed = int(json.load(f).get("seed", 0))
     dm = XmmDataModule(dcfg, splits, seed=seed).setup("test", device=dev, max_pool_bytes=max_pool_bytes)
-    model = load_model(checkpoint, name, lr_res, device=dev)
+    model = load_model(checkpoint, name, lr_res, device=dev, math=math)
     model.loss = create_loss(*load_loss_config(scaling)) if loss != "l1" else Loss({"l1": 1.0})
     model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
     if extended_metrics:
@@ -338,13 +338,15 @@ def main():
     ap.add_argument("--extended-metrics", action="store_true",
                     help="test (and fit's final test epoch): add vif_p, gmsd, ms_gmsd, haarpsi, msdi (get_ext_metrics / get_in_ext_metrics; no fsim)")
     a = ap.parse_args()
+    if a.routine == "test" and a.model == "restormer" and a.math not in (None, "fp32"):
+        ap.error(f"restormer: math mode {a.math!r} is not supported: the Restormer engine computes in 'fp32' only")
     ds = dict(dataset_name=a.dataset_name, dataset_type=a.dataset_type, lr_exps=tuple(a.lr_exps), hr_exp=a.hr_exp,
               lr_det_mask=a.lr_det_mask, hr_det_mask=a.hr_det_mask, agn=a.agn, lr_bkg=a.lr_bkg, comb_hr=a.comb_hr, splits=a.splits)
     if a.routine == "test":
         if not a.checkpoint or not a.dataset_dir:
             ap.error("test needs --checkpoint and --dataset-dir")
         test(a.checkpoint, a.dataset_dir, name=a.model, lr_res=a.lr_res, scaling=a.scaling, batch_size=a.batch_size, loss=a.loss,
-             seed=a.seed, extended_metrics=a.extended_metrics, **ds)
+             seed=a.seed, extended_metrics=a.extended_metrics, math=a.math, **ds)
     elif a.dataset_dir is None:
         fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling, val_batches=a.val_batches)
     else:
