@@ -245,6 +245,31 @@ int xsd_restormer_pack_weights(xsd_restormer* r, const float* dev_params, void* 
  * x: [B][inp_channels][H][W], y: [B][out_channels][H][W], H and W divisible by 8 (three PixelUnshuffle(2) levels), B >= 1.
  * A workspace that cannot fit is refused with XSD_ERR_NOMEM before anything is enqueued. */
 int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* The Restormer kernels on their own (tests).  Each runs the launch helper the forward runs, allocates its own scratch, refuses a shape
+ * outside its kernel's limits with XSD_ERR_ARG before any launch, and synchronises the stream.  All tensors NCHW fp32, B <= 65535 (the
+ * images are the grid's z), H W <= 2^28.
+ * The 1x1 conv: x [B][>= cin][HW] with a batch stride of xbs floats (>= cin HW: the first cin channels of a wider slab are read),
+ * y likewise with ybs and cout; dev_w [cout][cin] as a Conv2d stores it, or with per_image set [B][cout][cin], one matrix per image
+ * (the call transposes it to the [cin][cout] the kernel reads); dev_bias [cout] or NULL; ln 0 none, 1 WithBias, 2 BiasFree LayerNorm over
+ * the cin channels of each pixel in front (dev_lnw [cin], dev_lnb [cin], the latter unused by 2); with residual set y += conv(x) in place,
+ * else y = conv(x).  cin, cout <= 131072. */
+int xsd_restormer_test_pw(const float* dev_x, int64_t xbs, const float* dev_w, int per_image, const float* dev_bias, int ln, const float* dev_lnw,
+                          const float* dev_lnb, int residual, float* dev_y, int64_t ybs, int B, int cin, int cout, int64_t HW, void* stream);
+/* The depthwise 3x3 conv, zero padding 1, any H, W >= 1.  gate 0: x [B][cout][H][W], dev_w [cout][9], dev_bias [cout] or NULL ->
+ * y [B][cout][H][W].  gate 1: x [B][2 cout][H][W], dev_w [2 cout][9], dev_bias [2 cout] or NULL -> y = gelu(x1) * x2 of the two
+ * halves of the conv's channels (exact-erf GELU).  cout <= 65535. */
+int xsd_restormer_test_dw(const float* dev_x, const float* dev_w, const float* dev_bias, float* dev_y, int B, int cout, int gate, int H, int W,
+                          void* stream);
+/* The channel attention behind the depthwise conv (restormer.py:126-139): qkv [B][3 C][HW], temperature [heads], dev_wpo [C][C] and
+ * dev_bpo [C] or NULL project_out as stored; x [B][C][HW] in place: x += project_out(softmax(normalize(q) normalize(k)^T temperature) v).
+ * heads divides C into at most 64 channels per head, C <= 8192. */
+int xsd_restormer_test_attention(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x, int B,
+                                 int C, int heads, int64_t HW, void* stream);
+/* The dense 3x3 conv, zero padding 1: x [B][cin][H][W], dev_w [cout][cin][3][3], dev_bias [cout] or NULL, any H, W >= 1.
+ * mode 0: y [B][cout][H][W] (+ dev_skip [B][cout][H][W] unless NULL); mode 1: y = PixelUnshuffle(2) of it, [B][4 cout][H/2][W/2], H and W
+ * even; mode 2: y = PixelShuffle(2) of it, [B][cout/4][2 H][2 W], cout a multiple of 4.  dev_skip must be NULL in modes 1 and 2. */
+int xsd_restormer_test_conv3(const float* dev_x, const float* dev_w, const float* dev_bias, const float* dev_skip, float* dev_y, int B, int cin,
+                             int cout, int H, int W, int mode, void* stream);
 
 /* ---- SwinFIR super-resolution, forward only (csrc/swinfir.hip) ----------------------------------------------
  * The reference's SwinFIR (models/transformer/swinfir.py:120-441 with the Swin blocks of modules.py; factory models/model.py:187-200,
@@ -314,6 +339,16 @@ int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, i
  * the stream. */
 int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int conv3, int B, int H, int W, int cin,
                      int N, int64_t ldy, int act, float slope, int math, void* stream);
+/* The shifted-window attention that SwinFIR and HAT share, on its own (tests; modules.py:115-140 between the qkv Linear and proj, with the
+ * roll, window partition and reverse of :316-340): qkv [B][H W][3 C] token rows in image order (q, k, v; head h at channels h hd .. of
+ * each), table [(2 ws - 1)^2][heads] the relative-position bias -> out [B][H W][C] in image order.  With shift > 0 the windows are
+ * those of the image rolled by -shift and the -100 mask of the run-time size applies.  1 <= ws <= 16, H and W multiples of ws,
+ * 0 <= shift < ws, heads divides C into at most 32 channels per head.  Synchronises the stream. */
+int xsd_sw_test_attention(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int shift,
+                          float scale, void* stream);
+/* The token LayerNorm of both networks on its own (tests): x [M][C] -> y [M][C] = (x - mean) / sqrt(var + 1e-5) * w + b over the C
+ * channels of each row (biased variance), w and b [C]; 1 <= C <= 4096, 1 <= M <= 2^31.  Synchronises the stream. */
+int xsd_sw_test_layernorm(const float* dev_x, const float* dev_w, const float* dev_b, float* dev_y, int64_t M, int C, void* stream);
 
 /* ---- HAT super-resolution, forward only (csrc/hat.hip) ------------------------------------------------------
  * The reference's HAT (models/transformer/hat.py:10-913; factory models/model.py:216-229, XMM configuration res/configs/models.toml
@@ -376,6 +411,13 @@ int xsd_hat_test_ocab(const float* dev_qkv, const float* dev_table, float* dev_o
                       float scale, void* stream);
 /* the channel attention's AdaptiveAvgPool2d(1) on its own (hat.py:20): x [B][HW][C] token-major -> mean [B][C]; synchronises the stream */
 int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_t HW, int C, void* stream);
+/* what a HAB does with its CAB branch, on its own (tests; hat.py:20-29, :268): x and t [B][HW][C] token-major, dev_w1 [Cs][C], dev_b1
+ * [Cs], dev_w2 [C][Cs], dev_b2 [C] the squeeze MLP's 1x1 convs as stored: y[b] = sigmoid(w2 relu(w1 mean_p(t[b]) + b1) + b2), then
+ * x += (t * y[b]) * scale in place; dev_y [B][C] receives the gates unless NULL.  With dev_w1 NULL (then dev_y must be NULL and the other
+ * weights and Cs are ignored): the plain x += t * scale of the "identity" branches.  B <= 65535, HW <= 2^28, C and Cs in [1, 4096].
+ * Synchronises the stream. */
+int xsd_hat_test_ca_combine(float* dev_x, const float* dev_t, const float* dev_w1, const float* dev_b1, const float* dev_w2, const float* dev_b2,
+                            float scale, int B, int64_t HW, int C, int Cs, float* dev_y, void* stream);
 
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's

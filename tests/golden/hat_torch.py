@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import gen_hat as gh
-from swinfir_torch import _conv, _lin, _ln, _unwindows, _windows
+from swinfir_torch import _conv, _lin, _ln, _unwindows, _windows, window_attention
 
 
 def _mlp(t, sd, p):
@@ -35,23 +35,10 @@ def cab(u, sd, p):
 
 def _hab(t, sd, p, H, W, heads, ws, shift, scale, conv_scale):
     B, L, C = t.shape
-    hd = C // heads
-    n = ws * ws
-    u = _ln(t, sd, p + "norm1").view(B, H, W, C)
-    conv_x = cab(u.permute(0, 3, 1, 2), sd, p + "conv_block.").permute(0, 2, 3, 1).reshape(B, L, C)
-    s = torch.roll(u, shifts=(-shift, -shift), dims=(1, 2)) if shift else u
-    qkv = _lin(_windows(s, ws), sd, p + "attn.qkv").view(-1, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
-    a = (qkv[0] * scale) @ qkv[1].transpose(-2, -1)
-    idx = torch.from_numpy(gh.rel_index(ws)).to(t.device)
-    a = a + sd[p + "attn.relative_position_bias_table"][idx.view(-1)].view(n, n, heads).permute(2, 0, 1)[None]
-    if shift:
-        mask = torch.from_numpy(gh.shift_mask(H, W, ws, shift)).to(t.device, t.dtype)
-        a = (a.view(-1, mask.shape[0], heads, n, n) + mask[None, :, None]).view(-1, heads, n, n)
-    o = (a.softmax(-1) @ qkv[2]).transpose(1, 2).reshape(-1, n, C)
-    o = _unwindows(_lin(o, sd, p + "attn.proj"), ws, B, H, W)
-    if shift:
-        o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
-    t = t + o.reshape(B, L, C) + conv_x * conv_scale
+    u = _ln(t, sd, p + "norm1")
+    conv_x = cab(u.view(B, H, W, C).permute(0, 3, 1, 2), sd, p + "conv_block.").permute(0, 2, 3, 1).reshape(B, L, C)
+    o = window_attention(_lin(u, sd, p + "attn.qkv"), sd[p + "attn.relative_position_bias_table"], H, W, heads, ws, shift, scale)
+    t = t + _lin(o, sd, p + "attn.proj") + conv_x * conv_scale
     return _mlp(t, sd, p)
 
 

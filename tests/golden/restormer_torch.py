@@ -21,15 +21,22 @@ def _conv(x, sd, name, padding=0, groups=1):
     return F.conv2d(x, sd[name + ".weight"], sd.get(name + ".bias"), padding=padding, groups=groups)
 
 
-def _attention(x, sd, p, heads):
-    B, C, H, W = x.shape
-    qkv = _conv(_conv(x, sd, p + "qkv"), sd, p + "qkv_dwconv", padding=1, groups=3 * C)
+def channel_attention(qkv, temperature, heads):
+    """qkv [B, 3 C, H, W] as the depthwise conv leaves it, temperature [heads, 1, 1] -> softmax(normalize(q) normalize(k)^T temperature) v,
+    [B, C, H, W], the input of project_out (:126-139)"""
+    B, C3, H, W = qkv.shape
+    C = C3 // 3
     q, k, v = (t.reshape(B, heads, C // heads, H * W) for t in qkv.chunk(3, dim=1))
     q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)          # F.normalize(dim=-1), eps 1e-12
     k = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    attn = (q @ k.transpose(-2, -1)) * sd[p + "temperature"]
-    out = attn.softmax(dim=-1) @ v
-    return _conv(out.reshape(B, C, H, W), sd, p + "project_out")
+    attn = (q @ k.transpose(-2, -1)) * temperature
+    return (attn.softmax(dim=-1) @ v).reshape(B, C, H, W)
+
+
+def _attention(x, sd, p, heads):
+    C = x.shape[1]
+    qkv = _conv(_conv(x, sd, p + "qkv"), sd, p + "qkv_dwconv", padding=1, groups=3 * C)
+    return _conv(channel_attention(qkv, sd[p + "temperature"], heads), sd, p + "project_out")
 
 
 def _ffn(x, sd, p):

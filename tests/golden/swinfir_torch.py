@@ -36,28 +36,35 @@ def _unwindows(t, ws, B, H, W):
     return t.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
 
 
-def _swin_block(t, sd, p, H, W, heads, ws, shift, scale):
-    B, L, C = t.shape
-    hd = C // heads
-    u = _ln(t, sd, p + "norm1").view(B, H, W, C)
+def window_attention(qkv, table, H, W, heads, ws, shift, scale, masked=True):
+    """qkv [B, H W, 3 C] (the qkv Linear's output on the token rows, in image order), table [(2 ws - 1)^2, heads] -> [B, H W, C], the input
+    of proj in image order: roll by -shift, window partition, softmax(q scale k^T + table[index] (+ the -100 shift mask)) v, window
+    reverse, roll back.  masked=False leaves the shift mask out (for tests that must see it)."""
+    B, L, C3 = qkv.shape
+    C = C3 // 3
+    hd, n = C // heads, ws * ws
+    u = qkv.view(B, H, W, C3)
     if shift:
         u = torch.roll(u, shifts=(-shift, -shift), dims=(1, 2))
-    xw = _windows(u, ws)
-    n = ws * ws
-    qkv = _lin(xw, sd, p + "attn.qkv").view(-1, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
+    qkv = _windows(u, ws).view(-1, n, 3, heads, hd).permute(2, 0, 3, 1, 4)
     q, k, v = qkv[0] * scale, qkv[1], qkv[2]
     a = q @ k.transpose(-2, -1)
-    idx = torch.from_numpy(gs.rel_index(ws)).to(t.device)
-    a = a + sd[p + "attn.relative_position_bias_table"][idx.view(-1)].view(n, n, heads).permute(2, 0, 1)[None]
-    if shift:
-        mask = torch.from_numpy(gs.shift_mask(H, W, ws, shift)).to(t.device, t.dtype)
+    idx = torch.from_numpy(gs.rel_index(ws)).to(qkv.device)
+    a = a + table[idx.view(-1)].view(n, n, heads).permute(2, 0, 1)[None]
+    if shift and masked:
+        mask = torch.from_numpy(gs.shift_mask(H, W, ws, shift)).to(qkv.device, qkv.dtype)
         nw = mask.shape[0]
         a = (a.view(-1, nw, heads, n, n) + mask[None, :, None]).view(-1, heads, n, n)
-    o = (a.softmax(-1) @ v).transpose(1, 2).reshape(-1, n, C)
-    o = _unwindows(_lin(o, sd, p + "attn.proj"), ws, B, H, W)
+    o = _unwindows((a.softmax(-1) @ v).transpose(1, 2).reshape(-1, n, C), ws, B, H, W)
     if shift:
         o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
-    t = t + o.reshape(B, L, C)
+    return o.reshape(B, L, C)
+
+
+def _swin_block(t, sd, p, H, W, heads, ws, shift, scale):
+    qkv = _lin(_ln(t, sd, p + "norm1"), sd, p + "attn.qkv")
+    o = window_attention(qkv, sd[p + "attn.relative_position_bias_table"], H, W, heads, ws, shift, scale)
+    t = t + _lin(o, sd, p + "attn.proj")
     return t + _lin(F.gelu(_lin(_ln(t, sd, p + "norm2"), sd, p + "mlp.fc1")), sd, p + "mlp.fc2")
 
 

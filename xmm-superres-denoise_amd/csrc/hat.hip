@@ -249,6 +249,15 @@ hipError_t pool_partial(hipStream_t s, const float* x, double* part, int B, long
     return hipGetLastError();
 }
 
+// the gates y [B][C] (and / or the means) from the partial sums of pool_partial
+hipError_t ca(hipStream_t s, const double* part, int B, long long HW, int C, int Cs, const float* w1, const float* b1, const float* w2,
+              const float* b2, float* mean_out, float* y)
+{
+    hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(C + std::max(Cs, 1)), s, part, pool_chunks(HW), HW, C,
+                       Cs, w1, b1, w2, b2, mean_out, y);
+    return hipGetLastError();
+}
+
 hipError_t combine(hipStream_t s, float* x, const float* t, const float* y, float scale, int B, long long HW, int C)
 {
     const long long total = (long long)B * HW * C;
@@ -468,7 +477,6 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
     float* O = r->O;
     float* const XF = r->XF;
     double* const PART = (double*)r->PART;
-    const int nchunk = pool_chunks(HW);
     const float* wt = r->wt;
     hipError_t e = hipSuccess;
 #define HT(x) do { if ((e = (x)) != hipSuccess) return rfail(XSD_ERR_HIP, "HAT forward: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__); } while (0)
@@ -487,9 +495,7 @@ int xsd_hat_forward(xsd_hat* r, const float* dev_x, float* dev_y, int B, int H, 
             p = gp_conv(r->T1, B, H, W, r->Cc, wt + k.c2.t, E, PP(r, k.c2.b), r->T2, E);
             HT(gemm(s, r, p));
             HT(pool_partial(s, r->T2, PART, B, HW, E));
-            hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(E + r->Cs), s, PART, nchunk, HW, E, r->Cs,
-                               r->params + k.sq1.w, r->params + k.sq1.b, r->params + k.sq2.w, r->params + k.sq2.b, (float*)nullptr, r->YC);
-            HT(hipGetLastError());
+            HT(ca(s, PART, B, HW, E, r->Cs, r->params + k.sq1.w, r->params + k.sq1.b, r->params + k.sq2.w, r->params + k.sq2.b, nullptr, r->YC));
             // u is no longer needed: O takes the attention
             HT(attention(s, r->A, O, r->params + k.table, B, H, W, E, L.heads, r->ws, k.shift, attn_scale(c.qk_scale, E / L.heads)));
             p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
@@ -560,14 +566,48 @@ int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_
         return rfail(XSD_ERR_NOMEM, "HAT pool test: allocation failed");
     }
     hipError_t e = pool_partial(s, dev_x, part, B, HW, C);
-    if (!e) {
-        hipLaunchKernelGGL(hat_ca_kernel, dim3((unsigned)B), dim3(256), sizeof(float) * (size_t)(C + 1), s, part, nchunk, (long long)HW, C, 0,
-                           (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, dev_mean, (float*)nullptr);
-        e = hipGetLastError();
-    }
+    if (!e) e = ca(s, part, B, HW, C, 0, nullptr, nullptr, nullptr, nullptr, dev_mean, nullptr);
     hipStreamSynchronize(s);
     hipFree(part);
     if (e) return rfail(XSD_ERR_HIP, "HAT pool test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+// What a HAB does with its CAB branch t, on its own (tests): see include/xsd.h, xsd_hat_test_ca_combine.
+int xsd_hat_test_ca_combine(float* dev_x, const float* dev_t, const float* dev_w1, const float* dev_b1, const float* dev_w2, const float* dev_b2,
+                            float scale, int B, int64_t HW, int C, int Cs, float* dev_y, void* stream)
+{
+    if (!dev_x || !dev_t) return rfail(XSD_ERR_ARG, "null argument");
+    if (B < 1 || B > 65535) return rfail(XSD_ERR_ARG, "HAT combine test: %d images are outside [1, 65535]", B);
+    if (HW < 1 || HW > (1ll << 28)) return rfail(XSD_ERR_ARG, "HAT combine test: %lld pixels are outside [1, 2^28]", (long long)HW);
+    if (C < 1 || C > 4096) return rfail(XSD_ERR_ARG, "HAT combine test: %d channels are outside [1, 4096]", C);
+    if ((long long)B * HW * C > (1ll << 38)) return rfail(XSD_ERR_ARG, "HAT combine test: %d x %lld x %d elements are too many", B, (long long)HW, C);
+    hipStream_t s = (hipStream_t)stream;
+    if (!dev_w1) {                                  // the identity branches' x += t * scale
+        if (dev_y) return rfail(XSD_ERR_ARG, "HAT combine test: no gates to return without the squeeze weights");
+        hipError_t e = combine(s, dev_x, dev_t, nullptr, scale, B, HW, C);
+        hipStreamSynchronize(s);
+        if (e) return rfail(XSD_ERR_HIP, "HAT combine test: %s", hipGetErrorString(e));
+        return XSD_OK;
+    }
+    if (!dev_b1 || !dev_w2 || !dev_b2) return rfail(XSD_ERR_ARG, "HAT combine test: the squeeze MLP needs both weights and both biases");
+    if (Cs < 1 || Cs > 4096) return rfail(XSD_ERR_ARG, "HAT combine test: a squeezed width of %d is outside [1, 4096]", Cs);
+    double* part = nullptr;
+    float* gates = nullptr;
+    if (hipMalloc((void**)&part, sizeof(double) * (size_t)B * pool_chunks(HW) * C) != hipSuccess ||
+        hipMalloc((void**)&gates, sizeof(float) * (size_t)B * C) != hipSuccess) {
+        (void)hipGetLastError();
+        if (part) hipFree(part);
+        return rfail(XSD_ERR_NOMEM, "HAT combine test: allocation failed");
+    }
+    hipError_t e = pool_partial(s, dev_t, part, B, HW, C);
+    if (!e) e = ca(s, part, B, HW, C, Cs, dev_w1, dev_b1, dev_w2, dev_b2, nullptr, gates);
+    if (!e) e = combine(s, dev_x, dev_t, gates, scale, B, HW, C);
+    if (!e && dev_y) e = hipMemcpyAsync(dev_y, gates, sizeof(float) * (size_t)B * C, hipMemcpyDeviceToDevice, s);
+    hipStreamSynchronize(s);
+    hipFree(part);
+    hipFree(gates);
+    if (e) return rfail(XSD_ERR_HIP, "HAT combine test: %s", hipGetErrorString(e));
     return XSD_OK;
 }
 

@@ -21,7 +21,7 @@
 //   rst_attn_kernel    per image and head: combine the ranges (double, fixed order), F.normalize (eps 1e-12) as a division of the
 //                      Gram by the two norms, x temperature, softmax over the last dim, then fold project_out into it:
 //                      project_out(attn @ v) = (W_po blockdiag(attn_h)) v, i.e. a per-image C x C 1x1 conv applied to v.
-//   rst_conv3_kernel   dense 3x3 conv (patch_embed :160, Downsample / Upsample bodies, output :366) with plain,
+//   rst_conv3_kernel   dense 3x3 conv (patch_embed :160, Downsample / Upsample bodies, output :366; summed in double) with plain,
 //                      PixelUnshuffle(2) or PixelShuffle(2) store and the `+ inp_img` skip (:404).
 #include <hip/hip_runtime.h>
 
@@ -306,16 +306,18 @@ struct C3P {
 __global__ __launch_bounds__(256) void rst_conv3_kernel(const C3P P)
 {
     __shared__ float xin[C3CI][C3T + 2][C3T + 2];
-    __shared__ float wl[C3CO][C3CI][9];
+    __shared__ double wl[C3CO][C3CI][9];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int tilesX = (P.W + C3T - 1) / C3T;
     const int x0 = ((int)blockIdx.x % tilesX) * C3T, y0 = ((int)blockIdx.x / tilesX) * C3T;
     const int co0 = blockIdx.y * C3CO, b = blockIdx.z;
     const long long HW = (long long)P.H * P.W;
     const float* xb = P.x + (long long)b * P.xbs;
-    float acc[C3CO];
+    // the 9 cin products of an output are summed in double: in fp32 the chain's roundings alone put the result at 2-4x the error of a
+    // correctly rounded conv, which is what the fp32 yardstick delivers at these sizes
+    double acc[C3CO];
 #pragma unroll
-    for (int k = 0; k < C3CO; ++k) acc[k] = 0.f;
+    for (int k = 0; k < C3CO; ++k) acc[k] = 0.0;
     for (int ci0 = 0; ci0 < P.cin; ci0 += C3CI) {
         __syncthreads();
         for (int i = threadIdx.x; i < C3CI * (C3T + 2) * (C3T + 2); i += 256) {
@@ -328,18 +330,18 @@ __global__ __launch_bounds__(256) void rst_conv3_kernel(const C3P P)
         for (int i = threadIdx.x; i < C3CO * C3CI * 9; i += 256) {
             const int k = i / (C3CI * 9), r = i % (C3CI * 9), c = r / 9, t = r % 9;
             const int co = co0 + k, ci = ci0 + c;
-            wl[k][c][t] = (co < P.cout && ci < P.cin) ? P.w[((long long)co * P.cin + ci) * 9 + t] : 0.f;
+            wl[k][c][t] = (co < P.cout && ci < P.cin) ? (double)P.w[((long long)co * P.cin + ci) * 9 + t] : 0.0;
         }
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < C3CI; ++c) {
-            float v[9];
+            double v[9];
 #pragma unroll
-            for (int t = 0; t < 9; ++t) v[t] = xin[c][ty + t / 3][tx + t % 3];
+            for (int t = 0; t < 9; ++t) v[t] = (double)xin[c][ty + t / 3][tx + t % 3];
 #pragma unroll
             for (int k = 0; k < C3CO; ++k)
 #pragma unroll
-                for (int t = 0; t < 9; ++t) acc[k] = fmaf(wl[k][c][t], v[t], acc[k]);
+                for (int t = 0; t < 9; ++t) acc[k] = fma(wl[k][c][t], v[t], acc[k]);
         }
     }
     const int gx = x0 + tx, gy = y0 + ty;
@@ -348,7 +350,7 @@ __global__ __launch_bounds__(256) void rst_conv3_kernel(const C3P P)
     for (int k = 0; k < C3CO; ++k) {
         const int co = co0 + k;
         if (co >= P.cout) break;
-        float v = acc[k] + (P.bias ? P.bias[co] : 0.f);
+        float v = (float)(acc[k] + (P.bias ? (double)P.bias[co] : 0.0));
         long long o;
         if (P.mode == 1) o = (long long)(co * 4 + (gy & 1) * 2 + (gx & 1)) * (HW / 4) + (long long)(gy >> 1) * (P.W / 2) + (gx >> 1);
         else if (P.mode == 2) o = (long long)(co >> 2) * 4 * HW + (long long)(2 * gy + ((co >> 1) & 1)) * (2 * P.W) + 2 * gx + (co & 1);
@@ -490,34 +492,42 @@ hipError_t conv3(hipStream_t s, const float* x, long long xbs, int cin, const fl
     return hipGetLastError();
 }
 
+hipError_t dw(hipStream_t s, const float* x, long long xbs, const float* w, const float* bias, float* y, long long ybs, int cout, int gate, int H,
+              int W, int B)
+{
+    DwP p{x, xbs, w, bias, y, ybs, cout, gate, H, W};
+    const long long HW = (long long)H * W;
+    hipLaunchKernelGGL(rst_dw_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)cout, (unsigned)B), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+// x += project_out(softmax(normalize(q) normalize(k)^T temperature) v) (:126-139): qkv [B][3C][HW] with a batch stride of qbs, the Gram
+// partials into `part`, the per-image folded matrix into `mt`, then v through it as a per-image 1x1 conv onto X in place
+hipError_t attention(hipStream_t s, const float* qkv, long long qbs, const float* temp, const float* wpo_t, const float* bpo, double* part, float* mt,
+                     float* X, long long xbs, int C, int heads, long long HW, int B)
+{
+    const int nsplit = nsplit_of(HW, GRAM_CHUNK), ch = C / heads;
+    hipError_t e;
+    GramP p{qkv, qbs, C, ch, HW, GRAM_CHUNK, nsplit, part};
+    hipLaunchKernelGGL(rst_gram_kernel, dim3((unsigned)nsplit, (unsigned)heads, (unsigned)B), dim3(256), 0, s, p);
+    if ((e = hipGetLastError())) return e;
+    AttnP a{part, nsplit, temp, wpo_t, mt, C, ch};
+    hipLaunchKernelGGL(rst_attn_kernel, dim3((unsigned)heads, (unsigned)B), dim3(256), 0, s, a);
+    if ((e = hipGetLastError())) return e;
+    return pw(s, qkv + 2 * C * HW, qbs, C, nullptr, nullptr, 0, mt, (long long)C * C, bpo, X, xbs, X, xbs, C, HW, B);
+}
+
 // TransformerBlock (:156-170) in place on X: x += project_out(attn(norm1(x))); x += ffn(norm2(x))
 hipError_t block(xsd_restormer* r, hipStream_t s, const Blk& k, float* X, long long xbs, int H, int W)
 {
     const int B = r->B, C = k.C, ln = r->cfg.layernorm_bias_free ? 2 : 1;
     const long long HW = (long long)H * W;
-    const int nsplit = nsplit_of(HW, GRAM_CHUNK);
     hipError_t e;
     if ((e = pw(s, X, xbs, C, P(r, k.n1w), P(r, k.n1b), ln, r->wt + k.qkv.t, 0, P(r, k.qkv.b), nullptr, 0, r->Ta, 3 * C * HW, 3 * C, HW, B))) return e;
-    {
-        DwP p{r->Ta, 3 * C * HW, P(r, k.qkv_dw), P(r, k.qkv_dwb), r->Tb, 3 * C * HW, 3 * C, 0, H, W};
-        hipLaunchKernelGGL(rst_dw_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)(3 * C), (unsigned)B), dim3(256), 0, s, p);
-        if ((e = hipGetLastError())) return e;
-    }
-    {
-        GramP p{r->Tb, 3 * C * HW, C, k.ch, HW, GRAM_CHUNK, nsplit, (double*)r->part};
-        hipLaunchKernelGGL(rst_gram_kernel, dim3((unsigned)nsplit, (unsigned)k.heads, (unsigned)B), dim3(256), 0, s, p);
-        if ((e = hipGetLastError())) return e;
-        AttnP a{(const double*)r->part, nsplit, P(r, k.temp), r->wt + k.po.t, r->mt, C, k.ch};
-        hipLaunchKernelGGL(rst_attn_kernel, dim3((unsigned)k.heads, (unsigned)B), dim3(256), 0, s, a);
-        if ((e = hipGetLastError())) return e;
-    }
-    if ((e = pw(s, r->Tb + 2 * C * HW, 3 * C * HW, C, nullptr, nullptr, 0, r->mt, (long long)C * C, P(r, k.po.b), X, xbs, X, xbs, C, HW, B))) return e;
+    if ((e = dw(s, r->Ta, 3 * C * HW, P(r, k.qkv_dw), P(r, k.qkv_dwb), r->Tb, 3 * C * HW, 3 * C, 0, H, W, B))) return e;
+    if ((e = attention(s, r->Tb, 3 * C * HW, P(r, k.temp), r->wt + k.po.t, P(r, k.po.b), (double*)r->part, r->mt, X, xbs, C, k.heads, HW, B))) return e;
     if ((e = pw(s, X, xbs, C, P(r, k.n2w), P(r, k.n2b), ln, r->wt + k.pin.t, 0, P(r, k.pin.b), nullptr, 0, r->Ta, 2 * k.hid * HW, 2 * k.hid, HW, B))) return e;
-    {
-        DwP p{r->Ta, 2 * k.hid * HW, P(r, k.ffn_dw), P(r, k.ffn_dwb), r->Tb, k.hid * HW, k.hid, 1, H, W};
-        hipLaunchKernelGGL(rst_dw_kernel, dim3((unsigned)((HW + 255) / 256), (unsigned)k.hid, (unsigned)B), dim3(256), 0, s, p);
-        if ((e = hipGetLastError())) return e;
-    }
+    if ((e = dw(s, r->Ta, 2 * k.hid * HW, P(r, k.ffn_dw), P(r, k.ffn_dwb), r->Tb, k.hid * HW, k.hid, 1, H, W, B))) return e;
     return pw(s, r->Tb, k.hid * HW, k.hid, nullptr, nullptr, 0, r->wt + k.pout.t, 0, P(r, k.pout.b), X, xbs, X, xbs, C, HW, B);
 }
 
@@ -672,6 +682,125 @@ int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, in
     RST(conv3(s, r->slab1, s1, (int)(2 * d), r->params + r->outw, P(r, r->outb), dev_y, c.out_channels * HW1, c.out_channels, H, W, 0, dev_x,
               c.inp_channels * HW1, B));
 #undef RST
+    return XSD_OK;
+}
+
+// ---- the kernels on their own (tests): see include/xsd.h ----------------------------------------------------------------------
+
+namespace {
+
+// what every hook's launch grid needs: the images go to gridDim.z, channel groups to gridDim.y
+int check_grid(const char* what, int B, long long HW)
+{
+    if (B < 1 || B > 65535) return rfail(XSD_ERR_ARG, "%s: %d images are outside [1, 65535]", what, B);
+    if (HW < 1 || HW > (1ll << 28)) return rfail(XSD_ERR_ARG, "%s: %lld pixels are outside [1, 2^28]", what, HW);
+    return XSD_OK;
+}
+
+struct Scratch {                       // device allocations of one hook call
+    std::vector<void*> ptrs;
+    ~Scratch() { for (void* p : ptrs) hipFree(p); }
+    void* get(size_t bytes)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        ptrs.push_back(p);
+        return p;
+    }
+};
+
+hipError_t transpose(hipStream_t s, const float* src, float* dst, int rows, int cols)
+{
+    const long long n = (long long)rows * cols;
+    hipLaunchKernelGGL(rst_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, rows, cols);
+    return hipGetLastError();
+}
+
+} // namespace
+
+int xsd_restormer_test_pw(const float* dev_x, int64_t xbs, const float* dev_w, int per_image, const float* dev_bias, int ln, const float* dev_lnw,
+                          const float* dev_lnb, int residual, float* dev_y, int64_t ybs, int B, int cin, int cout, int64_t HW, void* stream)
+{
+    if (!dev_x || !dev_w || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
+    if (int rc = check_grid("Restormer 1x1 test", B, HW)) return rc;
+    if (cin < 1 || cin > 131072 || cout < 1 || cout > 131072)
+        return rfail(XSD_ERR_ARG, "Restormer 1x1 test: %d -> %d channels are outside [1, 131072]", cin, cout);
+    if (ln < 0 || ln > 2) return rfail(XSD_ERR_ARG, "Restormer 1x1 test: LayerNorm mode %d is not 0 (none), 1 (WithBias) or 2 (BiasFree)", ln);
+    if ((ln && !dev_lnw) || (ln == 1 && !dev_lnb)) return rfail(XSD_ERR_ARG, "Restormer 1x1 test: LayerNorm mode %d needs its weight%s", ln, ln == 1 ? " and bias" : "");
+    if (xbs < (int64_t)cin * HW || ybs < (int64_t)cout * HW)
+        return rfail(XSD_ERR_ARG, "Restormer 1x1 test: batch strides %lld / %lld are smaller than the %d / %d channels of %lld pixels", (long long)xbs,
+                     (long long)ybs, cin, cout, (long long)HW);
+    hipStream_t s = (hipStream_t)stream;
+    Scratch sc;
+    const int nw = per_image ? B : 1;
+    const long long wn = (long long)cin * cout;
+    float* wt = (float*)sc.get(sizeof(float) * (size_t)nw * wn);
+    if (!wt) return rfail(XSD_ERR_NOMEM, "Restormer 1x1 test: allocation failed");
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < nw && !e; ++i) e = transpose(s, dev_w + i * wn, wt + i * wn, cout, cin);
+    if (!e) e = pw(s, dev_x, xbs, cin, dev_lnw, dev_lnb, ln, wt, per_image ? wn : 0, dev_bias, residual ? dev_y : nullptr, residual ? ybs : 0, dev_y, ybs,
+                   cout, HW, B);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "Restormer 1x1 test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+int xsd_restormer_test_dw(const float* dev_x, const float* dev_w, const float* dev_bias, float* dev_y, int B, int cout, int gate, int H, int W,
+                          void* stream)
+{
+    if (!dev_x || !dev_w || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
+    if (H < 1 || W < 1) return rfail(XSD_ERR_ARG, "Restormer depthwise test: bad image size %d x %d", H, W);
+    const long long HW = (long long)H * W;
+    if (int rc = check_grid("Restormer depthwise test", B, HW)) return rc;
+    if (cout < 1 || cout > 65535) return rfail(XSD_ERR_ARG, "Restormer depthwise test: %d output channels are outside [1, 65535]", cout);
+    if (gate != 0 && gate != 1) return rfail(XSD_ERR_ARG, "Restormer depthwise test: mode %d is not 0 (plain) or 1 (gate)", gate);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = dw(s, dev_x, (gate ? 2 : 1) * cout * HW, dev_w, dev_bias, dev_y, cout * HW, cout, gate, H, W, B);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "Restormer depthwise test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+int xsd_restormer_test_attention(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x, int B,
+                                 int C, int heads, int64_t HW, void* stream)
+{
+    if (!dev_qkv || !dev_temperature || !dev_wpo || !dev_x) return rfail(XSD_ERR_ARG, "null argument");
+    if (int rc = check_grid("Restormer attention test", B, HW)) return rc;
+    if (heads < 1 || heads > 65535 || C < 1 || C % heads) return rfail(XSD_ERR_ARG, "Restormer attention test: %d heads do not divide %d channels", heads, C);
+    if (C / heads > AT_MAXCH)
+        return rfail(XSD_ERR_ARG, "Restormer attention test: %d channels per head; the kernels take at most %d", C / heads, AT_MAXCH);
+    if (C > 8192) return rfail(XSD_ERR_ARG, "Restormer attention test: %d channels are outside [1, 8192]", C);
+    hipStream_t s = (hipStream_t)stream;
+    const int ch = C / heads;
+    Scratch sc;
+    float* wt = (float*)sc.get(sizeof(float) * (size_t)C * C);
+    float* mt = (float*)sc.get(sizeof(float) * (size_t)B * C * C);
+    double* part = (double*)sc.get(sizeof(double) * (size_t)B * heads * nsplit_of(HW, GRAM_CHUNK) * (ch * ch + 2 * ch));
+    if (!wt || !mt || !part) return rfail(XSD_ERR_NOMEM, "Restormer attention test: allocation failed");
+    hipError_t e = transpose(s, dev_wpo, wt, C, C);
+    if (!e) e = attention(s, dev_qkv, 3 * C * HW, dev_temperature, wt, dev_bpo, part, mt, dev_x, C * HW, C, heads, HW, B);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "Restormer attention test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+int xsd_restormer_test_conv3(const float* dev_x, const float* dev_w, const float* dev_bias, const float* dev_skip, float* dev_y, int B, int cin,
+                             int cout, int H, int W, int mode, void* stream)
+{
+    if (!dev_x || !dev_w || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
+    if (H < 1 || W < 1) return rfail(XSD_ERR_ARG, "Restormer 3x3 test: bad image size %d x %d", H, W);
+    const long long HW = (long long)H * W;
+    if (int rc = check_grid("Restormer 3x3 test", B, HW)) return rc;
+    if (cin < 1 || cin > 131072 || cout < 1 || cout > 131072)
+        return rfail(XSD_ERR_ARG, "Restormer 3x3 test: %d -> %d channels are outside [1, 131072]", cin, cout);
+    if (mode < 0 || mode > 2) return rfail(XSD_ERR_ARG, "Restormer 3x3 test: mode %d is not 0 (plain), 1 (PixelUnshuffle) or 2 (PixelShuffle)", mode);
+    if (mode == 1 && (H % 2 || W % 2)) return rfail(XSD_ERR_ARG, "Restormer 3x3 test: PixelUnshuffle(2) needs even H and W; got %d x %d", H, W);
+    if (mode == 2 && cout % 4) return rfail(XSD_ERR_ARG, "Restormer 3x3 test: PixelShuffle(2) needs a multiple of 4 output channels; got %d", cout);
+    if (mode != 0 && dev_skip) return rfail(XSD_ERR_ARG, "Restormer 3x3 test: the skip is added in the plain mode only");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = conv3(s, dev_x, cin * HW, cin, dev_w, dev_bias, dev_y, cout * HW, cout, H, W, mode, dev_skip, cout * HW, B);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "Restormer 3x3 test: %s", hipGetErrorString(e));
     return XSD_OK;
 }
 

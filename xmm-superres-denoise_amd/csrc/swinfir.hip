@@ -496,4 +496,39 @@ int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bi
     return test_gemm(dev_a, dev_w, dev_bias, dev_y, conv3, B, H, W, cin, N, ldy, act, slope, math, (hipStream_t)stream);
 }
 
+// The shifted-window attention of both networks on its own (tests): see include/xsd.h, xsd_sw_test_attention.
+int xsd_sw_test_attention(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int shift,
+                          float scale, void* stream)
+{
+    if (!dev_qkv || !dev_table || !dev_out) return rfail(XSD_ERR_ARG, "null argument");
+    if (B < 1 || H < 1 || W < 1) return rfail(XSD_ERR_ARG, "window attention test: bad shape %dx%dx%d", B, H, W);
+    if (ws < 1 || ws > 16) return rfail(XSD_ERR_ARG, "window attention test: window size %d is outside [1, 16] (256 tokens per window)", ws);
+    if (H % ws || W % ws)
+        return rfail(XSD_ERR_ARG, "window attention test: H and W must be multiples of the window size %d; got %d x %d", ws, H, W);
+    if (shift < 0 || shift >= ws) return rfail(XSD_ERR_ARG, "window attention test: shift %d is outside [0, window size %d)", shift, ws);
+    if (heads < 1 || heads > 65535 || C < 1 || C % heads)
+        return rfail(XSD_ERR_ARG, "window attention test: %d heads do not divide %d channels", heads, C);
+    if (C / heads > 32) return rfail(XSD_ERR_ARG, "window attention test: head dim %d; the kernel takes at most 32", C / heads);
+    if ((long long)B * (H / ws) * (W / ws) > 0x7fffffffll || (long long)B * H * W > (1ll << 28))
+        return rfail(XSD_ERR_ARG, "window attention test: %d images of %d x %d tokens are too many", B, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = attention(s, dev_qkv, dev_out, dev_table, B, H, W, C, heads, ws, shift, scale);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "window attention test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
+// The token LayerNorm of both networks on its own (tests): see include/xsd.h, xsd_sw_test_layernorm.
+int xsd_sw_test_layernorm(const float* dev_x, const float* dev_w, const float* dev_b, float* dev_y, int64_t M, int C, void* stream)
+{
+    if (!dev_x || !dev_w || !dev_b || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
+    if (M < 1 || M > (1ll << 31)) return rfail(XSD_ERR_ARG, "LayerNorm test: %lld rows are outside [1, 2^31]", (long long)M);
+    if (C < 1 || C > 4096) return rfail(XSD_ERR_ARG, "LayerNorm test: %d channels are outside [1, 4096]", C);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = ln(s, dev_x, dev_y, dev_w, dev_b, M, C);
+    hipStreamSynchronize(s);
+    if (e) return rfail(XSD_ERR_HIP, "LayerNorm test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
 } // extern "C"

@@ -134,6 +134,13 @@ def load():
     L.xsd_sw_test_gemm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i64, i32, f32, i32, vp]
     L.xsd_hat_test_ocab.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     L.xsd_hat_test_channel_mean.argtypes = [fp, fp, i32, i64, i32, vp]
+    L.xsd_sw_test_attention.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.xsd_sw_test_layernorm.argtypes = [fp, fp, fp, fp, i64, i32, vp]
+    L.xsd_hat_test_ca_combine.argtypes = [fp, fp, fp, fp, fp, fp, f32, i32, i64, i32, i32, fp, vp]
+    L.xsd_restormer_test_pw.argtypes = [fp, i64, fp, i32, fp, i32, fp, fp, i32, fp, i64, i32, i32, i32, i64, vp]
+    L.xsd_restormer_test_dw.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
+    L.xsd_restormer_test_attention.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i64, vp]
+    L.xsd_restormer_test_conv3.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 
@@ -149,6 +156,8 @@ ABI_SYMBOLS = [
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
     "xsd_hat_create", "xsd_hat_destroy", "xsd_hat_param_count", "xsd_hat_pack_weights", "xsd_hat_forward", "xsd_hat_test_ocab",
     "xsd_hat_test_channel_mean", "xsd_hat_set_math", "xsd_hat_get_math",
+    "xsd_sw_test_attention", "xsd_sw_test_layernorm", "xsd_hat_test_ca_combine",
+    "xsd_restormer_test_pw", "xsd_restormer_test_dw", "xsd_restormer_test_attention", "xsd_restormer_test_conv3",
 ]
 
 

@@ -446,6 +446,203 @@ def hat_channel_mean(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _out_like(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    _require_cuda_f32(out, what)
+    if tuple(out.shape) != tuple(shape):
+        raise XsdError(f"{what} {tuple(out.shape)} is not {tuple(shape)}")
+    return out
+
+
+@_on_tensor_device
+def sw_window_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, heads: int, ws: int, shift: int, scale: float,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """The shifted-window attention of SwinFIR and HAT on its own (include/xsd.h: xsd_sw_test_attention): qkv [B, H W, 3 C] token rows in
+    image order (the qkv Linear's output), table [(2 ws - 1)^2, heads] -> [B, H W, C], the input of proj, in image order (into `out` if
+    given)."""
+    _require_cuda_f32(qkv, "qkv")
+    _require_cuda_f32(table, "table")
+    B, L, C3 = qkv.shape
+    if L != H * W or C3 % 3 or tuple(table.shape) != ((2 * ws - 1) ** 2, heads):
+        raise XsdError(f"qkv {tuple(qkv.shape)} / table {tuple(table.shape)} do not fit {H} x {W}, {heads} heads, window {ws}")
+    out = _out_like(out, (B, L, C3 // 3), qkv.device, "out")
+    check(_lib.load().xsd_sw_test_attention(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), B, H, W, C3 // 3, heads, ws, shift, float(scale),
+                                            _stream_ptr(qkv.device)))
+    return out
+
+
+@_on_tensor_device
+def sw_layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The token LayerNorm of SwinFIR and HAT on its own (include/xsd.h: xsd_sw_test_layernorm): x [M, C], w and b [C] -> [M, C].  With
+    `out` (2-D, C columns, at least M rows, contiguous) the result goes into its first M rows and nothing else of it is written."""
+    _require_cuda_f32(x, "x")
+    _require_cuda_f32(w, "w")
+    _require_cuda_f32(b, "b")
+    if x.dim() != 2 or w.numel() != x.shape[1] or b.numel() != x.shape[1]:
+        raise XsdError(f"x {tuple(x.shape)}, w {tuple(w.shape)} and b {tuple(b.shape)} are not [M, C], [C] and [C]")
+    M, C = (int(v) for v in x.shape)
+    if out is None:
+        out = torch.empty((M, C), device=x.device, dtype=torch.float32)
+    else:
+        _require_cuda_f32(out, "out")
+        if out.dim() != 2 or out.shape[0] < M or out.shape[1] != C:
+            raise XsdError(f"out {tuple(out.shape)} does not hold {M} rows of {C}")
+    check(_lib.load().xsd_sw_test_layernorm(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), M, C, _stream_ptr(x.device)))
+    return out
+
+
+@_on_tensor_device
+def hat_ca_combine(x: torch.Tensor, t: torch.Tensor, w1: torch.Tensor | None = None, b1: torch.Tensor | None = None,
+                   w2: torch.Tensor | None = None, b2: torch.Tensor | None = None, scale: float = 1.0,
+                   gates: torch.Tensor | None = None) -> torch.Tensor:
+    """What a HAB does with its CAB branch, on its own (include/xsd.h: xsd_hat_test_ca_combine): x, t [B, HW, C] token-major, w1 [Cs, C],
+    b1 [Cs], w2 [C, Cs], b2 [C] -> x += t * sigmoid(w2 relu(w1 mean(t) + b1) + b2) * scale IN PLACE (x is returned); `gates` [B, C]
+    receives the sigmoid gates.  Without w1: the plain x += t * scale."""
+    _require_cuda_f32(x, "x")
+    _require_cuda_f32(t, "t")
+    if x.dim() != 3 or x.shape != t.shape:
+        raise XsdError(f"x {tuple(x.shape)} and t {tuple(t.shape)} are not the same [B, HW, C]")
+    B, HW, C = (int(v) for v in x.shape)
+    Cs = 0
+    if w1 is not None:
+        for n, v in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+            _require_cuda_f32(v, n)
+        Cs = int(b1.numel())
+        if w1.numel() != Cs * C or w2.numel() != C * Cs or b2.numel() != C:
+            raise XsdError(f"w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, b2 {tuple(b2.shape)} are not a squeeze MLP of {C} channels")
+    if gates is not None:
+        _out_like(gates, (B, C), x.device, "gates")
+    check(_lib.load().xsd_hat_test_ca_combine(x.data_ptr(), t.data_ptr(), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), float(scale), B, HW, C, Cs,
+                                              _ptr(gates), _stream_ptr(x.device)))
+    return x
+
+
+RST_LN = {None: 0, "WithBias": 1, "BiasFree": 2}
+
+
+@_on_tensor_device
+def restormer_pw(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, ln: str | None = None,
+                 ln_weight: torch.Tensor | None = None, ln_bias: torch.Tensor | None = None, residual: bool = False,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Restormer's 1x1 conv on its own (include/xsd.h: xsd_restormer_test_pw): x [B, Cx, HW] of which the first cin channels are read,
+    w [cout, cin] as a Conv2d stores it or [B, cout, cin] (one matrix per image); ln None, "WithBias" or "BiasFree" (the channel LayerNorm
+    in front).  The result goes to the first cout channels of `out` [B, Cy, HW] (nothing else of it is written); with `residual` it is
+    added to them in place."""
+    _require_cuda_f32(x, "x")
+    _require_cuda_f32(w, "w")
+    if ln not in RST_LN:
+        raise XsdError(f"unknown LayerNorm type {ln!r}: {list(RST_LN)}")
+    if x.dim() != 3 or w.dim() not in (2, 3) or (w.dim() == 3 and w.shape[0] != x.shape[0]) or w.shape[-1] > x.shape[1]:
+        raise XsdError(f"x {tuple(x.shape)} and w {tuple(w.shape)} are not [B, >= cin, HW] and [(B,) cout, cin]")
+    B, Cx, HW = (int(v) for v in x.shape)
+    cout, cin = int(w.shape[-2]), int(w.shape[-1])
+    for n, v, k in (("bias", bias, cout), ("ln_weight", ln_weight, cin), ("ln_bias", ln_bias, cin)):
+        if v is not None:
+            _require_cuda_f32(v, n)
+            if v.numel() != k:
+                raise XsdError(f"{n} has {v.numel()} elements, not {k}")
+    if out is None:
+        if residual:
+            raise XsdError("residual needs the `out` it adds to")
+        out = torch.empty((B, cout, HW), device=x.device, dtype=torch.float32)
+    else:
+        _require_cuda_f32(out, "out")
+        if out.dim() != 3 or out.shape[0] != B or out.shape[1] < cout or out.shape[2] != HW:
+            raise XsdError(f"out {tuple(out.shape)} does not hold {B} x {cout} x {HW}")
+    check(_lib.load().xsd_restormer_test_pw(x.data_ptr(), Cx * HW, w.data_ptr(), int(w.dim() == 3), _ptr(bias), RST_LN[ln], _ptr(ln_weight),
+                                            _ptr(ln_bias), int(bool(residual)), out.data_ptr(), int(out.shape[1]) * HW, B, cin, cout, HW,
+                                            _stream_ptr(x.device)))
+    return out
+
+
+@_on_tensor_device
+def restormer_dw(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, gate: bool = False,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Restormer's depthwise 3x3 conv on its own (include/xsd.h: xsd_restormer_test_dw): x [B, Cin, H, W], w [Cin, 1, 3, 3] -> [B, Cin, H, W];
+    with `gate`, gelu(x1) * x2 of the conv's two channel halves -> [B, Cin / 2, H, W]."""
+    _require_cuda_f32(x, "x")
+    _require_cuda_f32(w, "w")
+    if x.dim() != 4 or w.numel() != 9 * x.shape[1] or (gate and x.shape[1] % 2):
+        raise XsdError(f"x {tuple(x.shape)} and w {tuple(w.shape)} are not [B, Cin, H, W] and [Cin, 1, 3, 3]")
+    B, Cin, H, W = (int(v) for v in x.shape)
+    if bias is not None:
+        _require_cuda_f32(bias, "bias")
+        if bias.numel() != Cin:
+            raise XsdError(f"bias has {bias.numel()} elements, not {Cin}")
+    cout = Cin // 2 if gate else Cin
+    out = _out_like(out, (B, cout, H, W), x.device, "out")
+    check(_lib.load().xsd_restormer_test_dw(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), B, cout, int(bool(gate)), H, W,
+                                            _stream_ptr(x.device)))
+    return out
+
+
+@_on_tensor_device
+def restormer_channel_attention(qkv: torch.Tensor, temperature: torch.Tensor, w_po: torch.Tensor, b_po: torch.Tensor | None,
+                                x: torch.Tensor, heads: int) -> torch.Tensor:
+    """Restormer's channel attention behind the depthwise conv, on its own (include/xsd.h: xsd_restormer_test_attention): qkv
+    [B, 3 C, HW], temperature [heads], w_po [C, C] (project_out as stored), b_po [C] or None; x [B, C, HW] is updated IN PLACE,
+    x += project_out(softmax(normalize(q) normalize(k)^T temperature) v), and returned."""
+    for n, v in (("qkv", qkv), ("temperature", temperature), ("w_po", w_po), ("x", x)):
+        _require_cuda_f32(v, n)
+    if x.dim() != 3 or tuple(qkv.shape) != (x.shape[0], 3 * x.shape[1], x.shape[2]) or w_po.numel() != x.shape[1] ** 2 or \
+            temperature.numel() != heads:
+        raise XsdError(f"qkv {tuple(qkv.shape)}, temperature {tuple(temperature.shape)}, w_po {tuple(w_po.shape)} and x {tuple(x.shape)} do not fit "
+                       f"[B, 3 C, HW], [{heads}], [C, C] and [B, C, HW]")
+    B, C, HW = (int(v) for v in x.shape)
+    if b_po is not None:
+        _require_cuda_f32(b_po, "b_po")
+        if b_po.numel() != C:
+            raise XsdError(f"b_po has {b_po.numel()} elements, not {C}")
+    check(_lib.load().xsd_restormer_test_attention(qkv.data_ptr(), temperature.data_ptr(), w_po.data_ptr(), _ptr(b_po), x.data_ptr(), B, C,
+                                                   int(heads), HW, _stream_ptr(x.device)))
+    return x
+
+
+RST_CONV3 = {None: 0, "unshuffle": 1, "shuffle": 2}
+
+
+@_on_tensor_device
+def restormer_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, skip: torch.Tensor | None = None,
+                      mode: str | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Restormer's dense 3x3 conv on its own (include/xsd.h: xsd_restormer_test_conv3): x [B, cin, H, W], w [cout, cin, 3, 3] ->
+    [B, cout, H, W] (+ skip); mode "unshuffle": PixelUnshuffle(2) of it, [B, 4 cout, H / 2, W / 2]; "shuffle": PixelShuffle(2) of it,
+    [B, cout / 4, 2 H, 2 W]."""
+    _require_cuda_f32(x, "x")
+    _require_cuda_f32(w, "w")
+    if mode not in RST_CONV3:
+        raise XsdError(f"unknown mode {mode!r}: {list(RST_CONV3)}")
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[1], 3, 3):
+        raise XsdError(f"x {tuple(x.shape)} and w {tuple(w.shape)} are not [B, cin, H, W] and [cout, cin, 3, 3]")
+    B, cin, H, W = (int(v) for v in x.shape)
+    cout = int(w.shape[0])
+    if bias is not None:
+        _require_cuda_f32(bias, "bias")
+        if bias.numel() != cout:
+            raise XsdError(f"bias has {bias.numel()} elements, not {cout}")
+    if skip is not None:
+        _require_cuda_f32(skip, "skip")
+        if tuple(skip.shape) != (B, cout, H, W):
+            raise XsdError(f"skip {tuple(skip.shape)} is not {(B, cout, H, W)}")
+    shape = (B, cout, H, W)
+    if mode == "unshuffle":
+        if H % 2 or W % 2:
+            raise XsdError(f"PixelUnshuffle(2) of {H} x {W} has no output shape: H and W must be even")
+        shape = (B, 4 * cout, H // 2, W // 2)
+    elif mode == "shuffle":
+        if cout % 4:
+            raise XsdError(f"PixelShuffle(2) of {cout} channels has no output shape: cout must be a multiple of 4")
+        shape = (B, cout // 4, 2 * H, 2 * W)
+    out = _out_like(out, shape, x.device, "out")
+    check(_lib.load().xsd_restormer_test_conv3(x.data_ptr(), w.data_ptr(), _ptr(bias), _ptr(skip), out.data_ptr(), B, cin, cout, H, W,
+                                               RST_CONV3[mode], _stream_ptr(x.device)))
+    return out
+
+
 class ExtMetricsEngine:
     """The extended test metrics of one batch (include/xsd.h: xsd_ext_metrics_eval): gmsd, ms_gmsd, haarpsi, mdsi and the two
     VIF sums per image, as doubles.  The formulas restate piq 0.7.x / torchmetrics 1.x from their published code; parity with
