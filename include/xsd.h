@@ -158,7 +158,7 @@ int xsd_loss_set_channels(xsd_loss_fn* f, int channels);
  * o=0.25; the reference's key spells it "msdi") and torchmetrics 1.x VisualInformationFidelity(sigma_n_sq=2.0).  The formulas are
  * restated from the libraries' published code (tests/golden/ext_metrics_torch.py holds them in plain torch):
  * neither library is available to this project, so parity with the libraries themselves is unpinned, as for psnr / ssim / ms_ssim.
- * fsim is not built (phase congruency needs 2-D FFTs of sizes the engine's FFT does not take, and a per-image median).
+ * fsim is not part of this call: it has its own object, xsd_fsim below.
  * preds, target: [B][H][W] fp32; values outside [0, 1] are not checked.  dev_out: B x XSD_EXTM_OUT device DOUBLES, per image
  *   [0] gmsd   [1] ms_gmsd   [2] haarpsi   [3] mdsi   [4] vif numerator   [5] vif denominator   (vif_p = [4] / [5]; a constant
  *   target gives 0 / 0 as in torchmetrics).
@@ -173,6 +173,36 @@ int xsd_ext_metrics_create(xsd_ext_metrics** out);
 void xsd_ext_metrics_destroy(xsd_ext_metrics* m);
 int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float* dev_target, double* dev_out, int B, int H, int W,
                          void* stream);
+
+/* The sixth extended test metric: piq 0.7.x fsim(x, y, chromatic=False) with every default (data_range=1, scales=4, orientations=4,
+ * min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, k=2.0) on single-channel images in [0, 1], restated from piq's published code
+ * (tests/golden/fsim_torch.py holds it in plain torch): parity with piq itself is unpinned.  csrc/fsim.hip.
+ * preds, target: [B][1][H][W] fp32.  dev_out: B device DOUBLES, one fsim value per image (per-image values, not the batch mean: the caller
+ * does the reference's reduction).  A pair without structure (sum of pc_max = 0, e.g. two all-zero images) gives NaN (0 / 0) as written.
+ * The images are pooled by ks = max(1, round_half_even(min(H, W) / 256)) to h x w = H / ks x W / ks (remainder dropped); what depends on
+ * (h, w) only -- the 16 log-Gabor filters, their noise constants, the two DFT matrices, all computed in double -- is a plan kept with the
+ * object; it holds the XSD_FSIM_PLANS most recently used sizes, so calls of two sizes can alternate without rebuilding.  The 2-D
+ * transforms are dense products with the DFT matrices (any length: no factorisation), accumulated in double; filter responses are stored
+ * fp32, every map and sum after them is double, summed in a fixed order without atomics: an image's value is bitwise independent of its
+ * batch-mates, of B and of the run, and a NaN / inf pixel makes its own image's value non-finite and no other's.  A fixed number of
+ * launches (9) whatever B is.  The workspace is sized at first use per (B, h, w) on the device that is current at that call: about
+ * 1008 h w bytes per image pair (the 32 inverse column transforms kept as complex doubles are 512 h w of them, the 32 fp32 responses
+ * 256 h w), i.e. 77 MB per pair at 277 x 277 and 157 + 78 MB for those two arrays at B = 4; it grows linearly with B and is never
+ * shrunk.  A workspace that cannot be allocated is refused with XSD_ERR_NOMEM before anything is enqueued.
+ * Refused with XSD_ERR_ARG and a message naming the limit: null pointers, B < 1 or > 2047, C != 1, a pooled side < 3 or > 1024. */
+#define XSD_FSIM_PLANS 4
+typedef struct xsd_fsim xsd_fsim;
+int xsd_fsim_create(xsd_fsim** out);
+void xsd_fsim_destroy(xsd_fsim* m);
+int xsd_fsim_eval(xsd_fsim* m, const float* dev_preds, const float* dev_target, double* dev_out, int B, int C, int H, int W, void* stream);
+/* Test entries, in the product library like xsd_sw_test_gemm.  test_dft2: the 2-D transform of xsd_fsim_eval alone, on B complex
+ * n1 x n2 arrays (interleaved re, im fp32; 3 <= n1, n2 <= 1024): forward (inverse = 0, no scaling) or inverse (1 / (n1 n2)), as
+ * torch.fft.fft2 / ifft2; every output element is written.  test_median: per row of n fp32 values the element torch.median picks (the
+ * lower of the two middle ones for even n), by radix select on the values' bit patterns; a row that holds a NaN gives NaN.  The keys
+ * order -0.0 below +0.0, which torch.median treats as equal: on a row that mixes the two the zero returned may carry the other sign
+ * (the engine's own rows are squares, never negative). */
+int xsd_fsim_test_dft2(xsd_fsim* m, const float* dev_in, float* dev_out, int B, int n1, int n2, int inverse, void* stream);
+int xsd_fsim_test_median(const float* dev_in, float* dev_out, int rows, int n, void* stream);
 
 /* torch.optim.Adam(lr, betas, eps=1e-8) single fused step over flat buffers (models/model.py:241-245).
  * step is 1-based; grad_scale multiplies the gradient on read (1/world_size for data-parallel mean). */

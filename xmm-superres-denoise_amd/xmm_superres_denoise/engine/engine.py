@@ -684,6 +684,72 @@ class ExtMetricsEngine:
         return out
 
 
+class FsimEngine:
+    """fsim of one batch (include/xsd.h: xsd_fsim_eval): piq 0.7.x fsim(chromatic=False) per image, as doubles.  The formula restates
+    piq's published code (tests/golden/fsim_torch.py); parity with piq itself is unpinned.  One object per GPU; it
+    owns a device workspace and the plans (filters, DFT matrices) of the pooled sizes it has seen most recently."""
+
+    def __init__(self):
+        self.L = _lib.load()
+        h = ctypes.c_void_p()
+        check(self.L.xsd_fsim_create(ctypes.byref(h)))
+        self.h = h
+        self.device_index = torch.cuda.current_device()     # the C side allocates and launches on the current device (see Engine)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                self.L.xsd_fsim_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _mine(self, t: torch.Tensor, name: str):
+        _require_cuda_f32(t, name)
+        if t.device.index != self.device_index:
+            raise XsdError(f"{name} is on cuda:{t.device.index}, this engine's workspace on cuda:{self.device_index}")
+
+    @_on_engine_device
+    def eval(self, preds: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """preds, target: [B, H, W] or [B, 1, H, W] fp32 in [0, 1] on this engine's device -> [B] float64 per-image fsim"""
+        self._mine(preds, "preds")
+        self._mine(target, "target")
+        if preds.shape != target.shape:
+            raise XsdError(f"shape mismatch {tuple(preds.shape)} vs {tuple(target.shape)}")
+        if preds.dim() == 3:
+            preds, target = preds[:, None], target[:, None]
+        if preds.dim() != 4:
+            raise XsdError(f"expected [B,H,W] or [B,1,H,W], got {tuple(preds.shape)}")
+        B, C, H, W = preds.shape
+        out = torch.empty((B,), device=preds.device, dtype=torch.float64)
+        check(self.L.xsd_fsim_eval(self.h, preds.data_ptr(), target.data_ptr(), out.data_ptr(), B, C, H, W, _stream_ptr(preds.device)))
+        return out
+
+    @_on_engine_device
+    def dft2(self, x: torch.Tensor, inverse: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The 2-D transform of the engine on its own (include/xsd.h: xsd_fsim_test_dft2): x [B, n1, n2, 2] fp32 (re, im) ->
+        torch.fft.fft2 / ifft2 of it in the same layout (into `out` if given)."""
+        self._mine(x, "x")
+        if x.dim() != 4 or x.shape[-1] != 2:
+            raise XsdError(f"expected [B, n1, n2, 2] (re, im), got {tuple(x.shape)}")
+        out = _out_like(out, x.shape, x.device, "out")
+        B, n1, n2, _ = x.shape
+        check(self.L.xsd_fsim_test_dft2(self.h, x.data_ptr(), out.data_ptr(), B, n1, n2, int(bool(inverse)), _stream_ptr(x.device)))
+        return out
+
+
+@_on_tensor_device
+def fsim_median(rows: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The exact selection of the fsim engine on its own (include/xsd.h: xsd_fsim_test_median): rows [R, n] fp32 -> [R], per row the
+    element torch.median picks (NaN for a row that holds a NaN), into `out` if given."""
+    _require_cuda_f32(rows, "rows")
+    if rows.dim() != 2:
+        raise XsdError(f"expected [rows, n], got {tuple(rows.shape)}")
+    out = _out_like(out, (rows.shape[0],), rows.device, "out")
+    check(_lib.load().xsd_fsim_test_median(rows.data_ptr(), out.data_ptr(), int(rows.shape[0]), int(rows.shape[1]), _stream_ptr(rows.device)))
+    return out
+
+
 def fft_size_supported(n: int) -> bool:
     """csrc/swinfir.hip: the FourierUnit's FFT takes lengths up to 4096 whose prime factors are all <= 13"""
     return bool(_lib.load().xsd_swinfir_fft_supported(int(n)))

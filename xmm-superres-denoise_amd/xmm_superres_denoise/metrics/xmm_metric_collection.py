@@ -20,7 +20,9 @@ reference's reductions (metrics/metrics.py:9-27) happen here, on the device, in 
           batch size to `total`: the quirk `poisson` shows too);
   vif_p   torchmetrics' own class: sum of per-image values / number of images.
 Their formulas restate piq 0.7.x / torchmetrics 1.x from the published code: parity with the libraries is unpinned (INTEGRATION.md
-section 3).  fsim is not built and is refused by name.
+section 3).  XMMExtMetricCollection refuses fsim by name (that refusal is pinned by tests); fsim is an opt-in collection of its own,
+XMMFsimCollection (get_fsim_metrics / get_in_fsim_metrics): one `xsd_fsim_eval` per (batch, stretch mode), the same `_Metric` reduction
+(sum of per-batch means / number of images), piq's formula restated in tests/golden/fsim_torch.py -- parity unpinned as well.
 """
 from __future__ import annotations
 
@@ -170,6 +172,81 @@ class XMMExtMetricCollection:
         return res
 
 
+class FsimEpochState:
+    """Epoch state of the reference's `_Metric` wrapper around piq.fsim (metrics/metrics.py:9-27,92-101), double, on the device of the
+    values: [sum of per-batch means, number of images]."""
+
+    def __init__(self):
+        self.acc = None
+
+    def add(self, per_image: torch.Tensor) -> None:
+        """per_image: [B] float64 of one batch: the BATCH MEAN goes to `metric`, B to `total`"""
+        v = per_image.double()
+        cur = torch.stack([v.mean(), v.new_tensor(float(v.shape[0]))])
+        self.acc = cur if self.acc is None else self.acc + cur
+
+    def sync(self, group=None, device=None) -> None:
+        """sum both states over the ranks; a rank that saw no batch takes part with zeros (see ExtEpochState.sync)"""
+        import torch.distributed as dist
+        from xmm_superres_denoise.parallel import all_reduce_any, collectives_on
+        if not collectives_on(group):
+            return
+        if self.acc is not None:
+            a = self.acc.clone()
+        else:
+            if device is None:
+                device = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
+            a = torch.zeros(2, dtype=torch.float64, device=device)
+        all_reduce_any(a, dist.ReduceOp.SUM, group)
+        self.acc = None if float(a[1]) == 0.0 else a
+
+    def compute(self) -> torch.Tensor:
+        return self.acc[0] / self.acc[1]
+
+
+class XMMFsimCollection:
+    """fsim beside XMMExtMetricCollection (which keeps refusing it by name): the same denorm -> renorm per scaling normaliser, keys
+    "<prefix>/<mode>/fsim" or, with `input_side`, "<prefix>/<mode>/in/fsim".  The formula restates piq 0.7.x fsim(chromatic=False) from its
+    published code: parity with piq is unpinned."""
+
+    def __init__(self, dataset_normalizer, scaling_normalizers: List, prefix: str, input_side: bool = False):
+        self.name = "in/fsim" if input_side else "fsim"
+        self.dataset_normalizer = dataset_normalizer
+        self.normalizer_dict = {n.stretch_mode: n for n in scaling_normalizers}
+        self.prefix = prefix
+        self._engines = {}       # one engine (device workspace + plans) per device
+        self.reset()
+
+    def reset(self):
+        self.states = {mode: FsimEpochState() for mode in self.normalizer_dict}
+
+    def _engine(self, device):
+        from ..engine.engine import FsimEngine
+        if device.index not in self._engines:
+            with torch.cuda.device(device):
+                self._engines[device.index] = FsimEngine()
+        return self._engines[device.index]
+
+    @torch.no_grad()
+    def update(self, preds: torch.Tensor, target: torch.Tensor) -> None:
+        if preds.dim() != 4 or preds.shape[1] != 1:
+            raise NotImplementedError(f"fsim: only single-channel [B, 1, H, W] images run on the MI355X engine (got {tuple(preds.shape)}; "
+                                      "piq's chromatic / YIQ branch is not built)")
+        preds = self.dataset_normalizer.denorm(preds)
+        target = self.dataset_normalizer.denorm(target)
+        for mode, normalizer in self.normalizer_dict.items():
+            p = normalizer.norm(preds).contiguous()
+            t = normalizer.norm(target).contiguous()
+            self.states[mode].add(self._engine(p.device).eval(p, t))
+
+    def sync(self, group=None) -> None:
+        for st in self.states.values():
+            st.sync(group)
+
+    def compute(self) -> dict:
+        return {f"{self.prefix}/{mode}/{self.name}": st.compute().float() for mode, st in self.states.items()}
+
+
 def get_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMMetricCollection:
     return XMMMetricCollection(NAMES, dataset_normalizer, scaling_normalizers, prefix)
 
@@ -185,3 +262,12 @@ def get_ext_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) 
 
 def get_in_ext_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMExtMetricCollection:
     return XMMExtMetricCollection(tuple("in/" + n for n in EXT_NAMES), dataset_normalizer, scaling_normalizers, prefix)
+
+
+def get_fsim_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMFsimCollection:
+    """the `fsim` entry of the reference's get_ext_metrics, as a collection of its own (opt-in: train --fsim)"""
+    return XMMFsimCollection(dataset_normalizer, scaling_normalizers, prefix)
+
+
+def get_in_fsim_metrics(dataset_normalizer, scaling_normalizers: List, prefix: str) -> XMMFsimCollection:
+    return XMMFsimCollection(dataset_normalizer, scaling_normalizers, prefix, input_side=True)

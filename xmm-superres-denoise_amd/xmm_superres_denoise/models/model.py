@@ -34,13 +34,16 @@ def _mean_over_ranks(values: dict) -> dict:
 
 class Model(nn.Module):
     def __init__(self, config: ModelCfg, lr_shape: Tuple[int, int], hr_shape: Tuple[int, int], loss=None,
-                 metrics=None, extended_metrics=None, in_metrics=None, in_extended_metrics=None):
+                 metrics=None, extended_metrics=None, in_metrics=None, in_extended_metrics=None, fsim_metrics=None,
+                 in_fsim_metrics=None):
         super().__init__()
         self.config = config
         self.metrics = metrics
         self.ext_metrics = extended_metrics
         self.in_metrics = in_metrics
         self.in_ext_metrics = in_extended_metrics
+        self.fsim_metrics = fsim_metrics            # opt-in, beside the extended set (metrics.XMMFsimCollection); None by default
+        self.in_fsim_metrics = in_fsim_metrics
         self.loss = loss
         self.model: Optional[nn.Module] = None
         self.hr_shape = hr_shape
@@ -136,7 +139,8 @@ class Model(nn.Module):
             return self.loss(preds, target)
         with torch.no_grad():
             self.loss.update(preds=preds, target=target)
-            if self.in_metrics is not None or self.ext_metrics is not None or self.in_ext_metrics is not None:
+            if (self.in_metrics is not None or self.ext_metrics is not None or self.in_ext_metrics is not None
+                    or self.in_fsim_metrics is not None):
                 scale_factor = target.shape[2] / lr_img.shape[2]
                 if scale_factor != 1.0:
                     from xmm_superres_denoise.transforms import ImageUpsample
@@ -149,6 +153,10 @@ class Model(nn.Module):
                 self.ext_metrics.update(preds=preds, target=target)
             if self.in_ext_metrics is not None:
                 self.in_ext_metrics.update(preds=lr_img, target=target)
+            if self.fsim_metrics is not None:
+                self.fsim_metrics.update(preds=preds, target=target)
+            if self.in_fsim_metrics is not None:
+                self.in_fsim_metrics.update(preds=lr_img, target=target)
         return None
 
     def _on_epoch_end(self, stage):
@@ -162,7 +170,7 @@ class Model(nn.Module):
         self.loss.sync()
         logged = {f"{stage}/loss": self.loss.compute()}
         self.loss.reset()
-        for name in ("metrics", "ext_metrics", "in_metrics", "in_ext_metrics"):
+        for name in ("metrics", "ext_metrics", "in_metrics", "in_ext_metrics", "fsim_metrics", "in_fsim_metrics"):
             coll = getattr(self, name)
             if coll is not None:
                 if hasattr(coll, "sync"):

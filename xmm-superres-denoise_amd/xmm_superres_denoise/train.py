@@ -7,7 +7,9 @@ data/dataset.py:52-74).  With `dataset_dir` it is the reference's XmmDataset (da
 into a device pool of raw FITS words, and each batch is one `xsd_compose_batch` launch per resolution (img + agn +
 background, mask, upsample, pad, normalize); `fit` then validates every epoch, keeps the best val/loss checkpoint and tests it,
 and `test` evaluates a checkpoint on the test split.  `extended_metrics=True` (CLI --extended-metrics) adds the reference's
-get_ext_metrics / get_in_ext_metrics to the test epoch (vif_p, gmsd, ms_gmsd, haarpsi, msdi; fsim is not built).
+get_ext_metrics / get_in_ext_metrics to the test epoch (vif_p, gmsd, ms_gmsd, haarpsi, msdi; without fsim).  `fsim=True` (CLI --fsim),
+independent of it, adds the sixth metric as key families of its own, test/<mode>/fsim and test/<mode>/in/fsim (csrc/fsim.hip; parity
+unpinned): opt-in, because the extended collection's refusal of fsim and its notice text are pinned by tests.
 
 Checkpoints use the reference's Lightning layout: {"state_dict": {"model.<key>": tensor}} with the reference key names,
 so `Model.load_from_checkpoint`-style consumers (utils/run_inference_on_file.py:28-35) can read them.
@@ -64,7 +66,7 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
         loss: str = "l1", scaling: str = "linear", val_batches: int = 0, dataset_dir: str | None = None,
         dataset_name: str = "sim_dataset", dataset_type: str = "sim", lr_exps=(20,), hr_exp: int = 100, epochs: int = 1,
         lr_det_mask: str | None = None, hr_det_mask: str | None = None, agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False,
-        splits: str | None = None, max_pool_bytes: int | None = None, extended_metrics: bool = False):
+        splits: str | None = None, max_pool_bytes: int | None = None, extended_metrics: bool = False, fsim: bool = False):
     """loss: "l1" (BASELINE configs[2]) or "paper" = the reference's shipped default, 0.5 psnr + 0.5 ms_ssim with the
     scaling table of the dataset's stretch mode (`scaling`; res/configs/loss_functions.toml, train.py:46-63).
 
@@ -74,7 +76,8 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
     `linear` normaliser, train.py:72-88); the checkpoint of the lowest val/loss is kept (ModelCheckpoint(monitor="val/loss",
     mode="min")), then a test epoch runs on it.  `scaling` is then the dataset's stretch; lr_res is the dataset's lr.res.
     The split JSON goes to `splits` (default: next to the checkpoint).  `extended_metrics` adds get_ext_metrics / get_in_ext_metrics
-    to that final test epoch only (the reference builds them only for `test`, train.py:90-102)."""
+    to that final test epoch only (the reference builds them only for `test`, train.py:90-102); `fsim` adds get_fsim_metrics /
+    get_in_fsim_metrics to the same epoch, with or without `extended_metrics`."""
     if name == "restormer":
         raise NotImplementedError("restormer: training Restormer is not on the MI355X engine (forward only: inference, infer.py, "
                                   "validation / test metrics); fit supports rrdb_denoise and esr_gen")
@@ -109,7 +112,7 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
         return _fit_dataset(name, batch_size, dev, rank, world, checkpoint, seed, math, log_every, loss, scaling,
                             dataset_cfg(dataset_dir, dataset_name, dataset_type, name, lr_res, lr_exps, hr_exp, lr_det_mask,
                                         hr_det_mask, agn, lr_bkg, comb_hr, scaling, batch_size),
-                            epochs, splits, max_pool_bytes, extended_metrics)
+                            epochs, splits, max_pool_bytes, extended_metrics, fsim)
     cfg = model_cfg(name, batch_size=batch_size)
     hr_res = lr_res * (2 if name == "esr_gen" else 1)
     torch.manual_seed(seed)
@@ -185,11 +188,36 @@ def _ext_metric_sets(dcfg, stage: str):
     return get_ext_metrics(norm, lin, stage), get_in_ext_metrics(norm, lin, stage)
 
 
+def _fsim_metric_sets(dcfg, stage: str):
+    """get_fsim_metrics / get_in_fsim_metrics (the `fsim` entry of the reference's extended set), same normalisers"""
+    from xmm_superres_denoise.metrics import get_fsim_metrics, get_in_fsim_metrics
+    from xmm_superres_denoise.transforms import Normalize
+    norm = Normalize(lr_max=dcfg.lr.clamp_max, hr_max=dcfg.hr.clamp_max, stretch_mode=dcfg.scaling)
+    lin = [Normalize(lr_max=dcfg.lr.clamp_max, hr_max=dcfg.hr.clamp_max, stretch_mode="linear")]
+    return get_fsim_metrics(norm, lin, stage), get_in_fsim_metrics(norm, lin, stage)
+
+
 EXT_METRICS_NOTICE = ("test: the extended metric collection (get_ext_metrics / get_in_ext_metrics: piq and VIF) is not on the "
                       "MI355X engine and is not computed; reported: loss, get_metrics and get_in_metrics")
 EXT_METRICS_ON_NOTICE = ("test: extended metrics (get_ext_metrics / get_in_ext_metrics) computed on the MI355X engine: vif_p, gmsd, ms_gmsd, "
                          "haarpsi, msdi (formulas restated from piq / torchmetrics: parity unpinned); fsim is the only metric left out "
                          "(not on the engine: it needs 2-D FFTs of sizes the engine's FFT does not take and a per-image median)")
+
+
+FSIM_ON_NOTICE = ("test: fsim (--fsim: get_fsim_metrics / get_in_fsim_metrics) computed on the MI355X engine (formula restated from piq: "
+                  "parity unpinned)")
+EXT_AND_FSIM_ON_NOTICE = ("test: extended metrics (get_ext_metrics / get_in_ext_metrics) and fsim (get_fsim_metrics / get_in_fsim_metrics) "
+                          "computed on the MI355X engine: vif_p, gmsd, ms_gmsd, haarpsi, msdi, fsim -- the reference's whole extended set "
+                          "(formulas restated from piq / torchmetrics: parity unpinned)")
+
+
+def _notices(extended_metrics: bool, fsim: bool) -> list:
+    """what a test epoch says about the extended metrics; without `fsim` exactly what it said before the flag existed"""
+    if extended_metrics and fsim:
+        return [EXT_AND_FSIM_ON_NOTICE]
+    if fsim:
+        return [EXT_METRICS_NOTICE, FSIM_ON_NOTICE]
+    return [EXT_METRICS_ON_NOTICE if extended_metrics else EXT_METRICS_NOTICE]
 
 
 def _eval_epoch(model: Model, dm, stage: str, per_rank: int, epoch: int) -> dict:
@@ -208,7 +236,7 @@ def _print_logged(title: str, logged: dict) -> None:
 
 
 def _fit_dataset(name, batch_size, dev, rank, world, checkpoint, seed, math, log_every, loss, scaling, dcfg, epochs, splits,
-                 max_pool_bytes, extended_metrics=False):
+                 max_pool_bytes, extended_metrics=False, fsim=False):
     from xmm_superres_denoise.data.datamodule import XmmDataModule
     from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
     cfg = model_cfg(name, batch_size=batch_size)
@@ -257,10 +285,12 @@ def _fit_dataset(name, batch_size, dev, rank, world, checkpoint, seed, math, log
     model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
     if extended_metrics:
         model.ext_metrics, model.in_ext_metrics = _ext_metric_sets(dcfg, "test")
+    if fsim:
+        model.fsim_metrics, model.in_fsim_metrics = _fsim_metric_sets(dcfg, "test")
     test_logged = _eval_epoch(model, dm, "test", per_rank, 0)
     if rank == 0 and log_every:
         _print_logged(f"test (best val/loss {best:.6f})", test_logged)
-        print(EXT_METRICS_ON_NOTICE if extended_metrics else EXT_METRICS_NOTICE, flush=True)
+        print("\n".join(_notices(extended_metrics, fsim)), flush=True)
     model.history, model.test_logged = history, test_logged
     return model, trainer, losses
 
@@ -269,14 +299,16 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
          dataset_type: str = "sim", lr_res: int = 416, lr_exps=(20,), hr_exp: int = 100, lr_det_mask=None, hr_det_mask=None,
          agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False, scaling: str = "linear", batch_size: int = 4, loss: str = "l1",
          seed: int | None = None, splits: str | None = None, device: str | None = None, max_pool_bytes: int | None = None,
-         log: bool = True, extended_metrics: bool = False, math: str | None = None) -> dict:
+         log: bool = True, extended_metrics: bool = False, math: str | None = None, fsim: bool = False) -> dict:
     """The reference's `train.py test` (train.py:91-103,165-171) on one device: the test split of the dataset through the model
     of `checkpoint` (any model infer.load_model loads), returning the `test/...` values (loss, get_metrics, get_in_metrics).
     The split file must be the one `fit` wrote (default location: next to the checkpoint); `seed` defaults to the one recorded
     there, so the test samples draw the same realisations, AGN and backgrounds as fit's test epoch.  Without `extended_metrics` the
     extended piq / VIF collection is not computed and the routine says so (EXT_METRICS_NOTICE) instead of leaving it out silently; with
     it, get_ext_metrics / get_in_ext_metrics (vif_p, gmsd, ms_gmsd, haarpsi, msdi) are added and the notice names fsim as the one
-    metric left out.  `math` is infer.load_model's: the math mode of the network (None: its default)."""
+    metric left out.  `fsim` adds get_fsim_metrics / get_in_fsim_metrics (test/<mode>/fsim, test/<mode>/in/fsim; parity unpinned) for any of
+    the five models, with or without `extended_metrics`, and says so (FSIM_ON_NOTICE, or one combined notice when both are given).
+    `math` is infer.load_model's: the math mode of the network (None: its default)."""
     from xmm_superres_denoise.data.datamodule import XmmDataModule
     from xmm_superres_denoise.infer import load_model
     from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
@@ -299,12 +331,14 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
     model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
     if extended_metrics:
         model.ext_metrics, model.in_ext_metrics = _ext_metric_sets(dcfg, "test")
+    if fsim:
+        model.fsim_metrics, model.in_fsim_metrics = _fsim_metric_sets(dcfg, "test")
     with torch.no_grad():
         logged = _eval_epoch(model, dm, "test", batch_size, 0)
     logged = {k: float(v) for k, v in logged.items()}
     if log:
         _print_logged("test", logged)
-        print(EXT_METRICS_ON_NOTICE if extended_metrics else EXT_METRICS_NOTICE, flush=True)
+        print("\n".join(_notices(extended_metrics, fsim)), flush=True)
     return logged
 
 
@@ -337,6 +371,9 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="fit: default 0; test: default the seed recorded in the split file")
     ap.add_argument("--extended-metrics", action="store_true",
                     help="test (and fit's final test epoch): add vif_p, gmsd, ms_gmsd, haarpsi, msdi (get_ext_metrics / get_in_ext_metrics; no fsim)")
+    ap.add_argument("--fsim", action="store_true",
+                    help="test (and fit's final test epoch): add fsim as test/<mode>/fsim and test/<mode>/in/fsim (parity unpinned); "
+                         "independent of --extended-metrics")
     a = ap.parse_args()
     if a.routine == "test" and a.model == "restormer" and a.math not in (None, "fp32"):
         ap.error(f"restormer: math mode {a.math!r} is not supported: the Restormer engine computes in 'fp32' only")
@@ -346,12 +383,12 @@ def main():
         if not a.checkpoint or not a.dataset_dir:
             ap.error("test needs --checkpoint and --dataset-dir")
         test(a.checkpoint, a.dataset_dir, name=a.model, lr_res=a.lr_res, scaling=a.scaling, batch_size=a.batch_size, loss=a.loss,
-             seed=a.seed, extended_metrics=a.extended_metrics, math=a.math, **ds)
+             seed=a.seed, extended_metrics=a.extended_metrics, math=a.math, fsim=a.fsim, **ds)
     elif a.dataset_dir is None:
         fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling, val_batches=a.val_batches)
     else:
         fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling,
-            seed=0 if a.seed is None else a.seed, dataset_dir=a.dataset_dir, epochs=a.epochs, extended_metrics=a.extended_metrics, **ds)
+            seed=0 if a.seed is None else a.seed, dataset_dir=a.dataset_dir, epochs=a.epochs, extended_metrics=a.extended_metrics, fsim=a.fsim, **ds)
     if dist.is_initialized():
         dist.destroy_process_group()
 
