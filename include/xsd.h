@@ -449,6 +449,69 @@ int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_
 int xsd_hat_test_ca_combine(float* dev_x, const float* dev_t, const float* dev_w1, const float* dev_b1, const float* dev_w2, const float* dev_b2,
                             float scale, int B, int64_t HW, int C, int Cs, float* dev_y, void* stream);
 
+/* ---- SwinIR restoration / super-resolution, forward only (csrc/swinir.hip) ----------------------------------
+ * The reference's SwinIR (models/transformer/swinir.py:133-395 with the Swin blocks of modules.py; exported by models/transformer but
+ * with no factory entry and no models.toml name).  Eval-mode forward in exact fp32 on SwinFIR's kernels (GEMM / conv3x3, window attention,
+ * LayerNorm, the per-block launch sequence), with all four reconstruction heads and both resi_connection forms.  Unlike SwinFIR and HAT
+ * it takes ANY image size: H and W are reflect-padded on the right and bottom to multiples of window_size and the output is cropped
+ * back (check_image_size, swinir.py:328-333, :395).  No float atomics: outputs are bitwise reproducible and each image's output is
+ * independent of the batch it is computed in; a NaN stays in its image.
+ * Flat parameter layout: fp32, the order of SwinIR.parameters(): conv_first.*, patch_embed.norm.* (patch_norm), per layer i and block j
+ * layers.i.residual_group.blocks.j.{norm1.*, attn.relative_position_bias_table, attn.qkv.weight[, .bias], attn.proj.*, norm2.*, mlp.fc1.*,
+ * mlp.fc2.*}, then layers.i.conv.* ("1conv") or layers.i.conv.{0,2,4}.* ("3conv"); norm.*; conv_after_body.* or conv_after_body.{0,2,4}.*;
+ * then the head -- "pixelshuffle": conv_before_upsample.0.*, upsample.{0,2,..}.*, conv_last.*; "pixelshuffledirect": upsample.0.*;
+ * "nearest+conv": conv_before_upsample.0.*, conv_up1.*, conv_up2.* (upscale 4 only), conv_hr.*, conv_last.*; "": conv_last.*.  The buffers
+ * relative_position_index and attn_mask are not in it: the engine computes both from the configuration and the run-time size. */
+typedef struct xsd_swinir xsd_swinir;
+typedef struct xsd_swinir_config {    /* SwinIR.__init__ arguments (swinir.py:161-184) */
+    int32_t img_size[2];           /* (H, W); with patch_size it sets the effective window: min(img // patch) if <= window_size, and then no
+                                      block shifts (SwinTransformerBlock.__init__, modules.py:236-239) */
+    int32_t patch_size[2];
+    int32_t in_chans;              /* 1..64 (3: the reference subtracts its RGB mean, swinir.py:190-194) */
+    int32_t embed_dim;             /* 2..4096; >= 4 with "3conv" */
+    int32_t num_layers;            /* 0..16 */
+    int32_t depths[16];            /* 0..64 each */
+    int32_t num_heads[16];         /* divides embed_dim into at most 32 channels per head */
+    int32_t window_size;           /* the pad goes to multiples of this; the effective window must be <= 16 */
+    int32_t qkv_bias;              /* 0/1 */
+    int32_t ape;                   /* must be 0 (refused) */
+    int32_t patch_norm;            /* 0/1 */
+    int32_t upscale;               /* 1, 2, 3, 4, 8; "nearest+conv": 2 or 4 */
+    int32_t upsampler;             /* 0 = "pixelshuffle", 1 = "pixelshuffledirect", 2 = "nearest+conv", 3 = "" (denoising: x + conv_last(res)) */
+    int32_t resi_connection;       /* 0 = "1conv", 1 = "3conv" */
+    double mlp_ratio;              /* hidden width (int)(embed_dim * mlp_ratio) */
+    double qk_scale;               /* 0: head_dim^-0.5 (the reference's `qk_scale or ...`); > 0 as given; < 0 refused */
+    double img_range;              /* > 0 */
+} xsd_swinir_config;
+/* replaces SwinIR.__init__ (swinir.py:161-318; engine state only, weights stay in the caller's flat buffer).  Refused with XSD_ERR_ARG
+ * and a message that names the argument: ape, an effective window > 16, a head dim > 32, embed_dim < 4 with "3conv", "nearest+conv" with
+ * an upscale other than 2 or 4 (the reference's output size would disagree with upscale), an upscale outside {1, 2, 3, 4, 8}. */
+int xsd_swinir_create(const xsd_swinir_config* cfg, xsd_swinir** out);
+void xsd_swinir_destroy(xsd_swinir* r);
+int64_t xsd_swinir_param_count(const xsd_swinir* r);
+/* the engine's weight-layout step, as xsd_swinfir_pack_weights: after every parameter update, before forward */
+int xsd_swinir_pack_weights(xsd_swinir* r, const float* dev_params, void* stream);
+/* replaces SwinIR.forward (swinir.py:350-395 with check_image_size :328-333, forward_features :335-348, RSTB.forward :114-120,
+ * UpsampleOneStep modules.py:398-415; Model.forward's clamp is not part of it).  x: [B][in_chans][H][W], any H and W >= 1;
+ * y: [B][in_chans][Ho][Wo] contiguous, (Ho, Wo) = xsd_swinir_out_size.  Refused with XSD_ERR_ARG before anything is enqueued: a pad that
+ * is not smaller than the image (F.pad's reflect raises there), and a padded size that is no multiple of the effective window (when
+ * img_size // patch_size clamped it; the reference fails in window_partition).  A workspace that cannot fit: XSD_ERR_NOMEM. */
+int xsd_swinir_forward(xsd_swinir* r, const float* dev_x, float* dev_y, int B, int H, int W, void* stream);
+/* the size of forward's output for an H x W input: x[:, :, :H * upscale, :W * upscale] (swinir.py:395) of what the head produced */
+int xsd_swinir_out_size(const xsd_swinir* r, int H, int W, int* Ho, int* Wo);
+/* Math mode of the engine's GEMMs: exactly xsd_swinfir_set_math above (0 = "fp32", 3 = "bf16x6"; 4, "f16x3", is refused by name) */
+int xsd_swinir_set_math(xsd_swinir* r, int mode);
+int xsd_swinir_get_math(const xsd_swinir* r);
+/* check_image_size and the input affine on their own (tests; swinir.py:328-333, :355): x [B][C][H][W] -> y [B][C][Hp][Wp] =
+ * (F.pad(x, (0, Wp - W, 0, Hp - H), "reflect") - mean) * img_range, Hp and Wp the multiples of ws; every element of y is written.
+ * mean: C floats in HOST memory, or NULL for zeros.  Synchronises the stream. */
+int xsd_swinir_test_pad(const float* dev_x, float* dev_y, int B, int C, int H, int W, int ws, const float* mean, float img_range, void* stream);
+/* conv_up1 / conv_up2 with their activation on their own (tests; swinir.py:373-385): a [B][H W][cin] token-major, dev_w [N][cin][3][3],
+ * dev_bias [N] or NULL -> y [B][4 H W][N] token-major = LeakyReLU_slope(conv3x3(nearest2x(a))), zero padding 1 at the 2 H x 2 W extent;
+ * the upsampled image is never stored.  math 0 (fp32) or 3 (bf16x6).  Synchronises the stream. */
+int xsd_swinir_test_nearest_conv(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int B, int H, int W, int cin, int N,
+                                 float slope, int math, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

@@ -1,4 +1,4 @@
-// sw_gemm_s3x.h -- the "bf16x6" (strict split) form of sw_kernels.h's GEMM, the opt-in math mode 3 of the SwinFIR and HAT engines.
+// sw_gemm_s3x.h -- the "bf16x6" (strict split) form of sw_kernels.h's GEMM, the opt-in math mode 3 of the SwinFIR, HAT and SwinIR engines.
 //
 // Same GemmP, same A modes (token rows; implicit im2col of a 3x3 conv over NCHW or token-major input with the input affine), same
 // epilogues and stores as sw_gemm_kernel.  Every fp32 operand is split EXACTLY into hi + mid + lo bf16 (xsd_split.h) and a product is
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void sw_gemm_s3x_kernel(const GemmP P, const u
                 const int yy = ry[i] + dy, xx = rx[i] + dx;
                 xsd::split_f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (rok[i] && kok && yy >= 0 && yy < P.H && xx >= 0 && xx < P.W)
-                    v = *reinterpret_cast<const xsd::split_f32x4*>(P.a + rbase[i] + ci + ((long long)yy * P.W + xx) * P.aps);
+                    v = *reinterpret_cast<const xsd::split_f32x4*>(P.a + rbase[i] + ci + SW_GEMM_EXT_SRC(yy, xx) * P.aps);
                 av[i] = v;
             }
         } else {
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void sw_gemm_s3x_kernel(const GemmP P, const u
                     const int yy = ry[i] + dy, xx = rx[i] + dx;
                     float v = 0.f;
                     if (rok[i] && kok && yy >= 0 && yy < P.H && xx >= 0 && xx < P.W) {
-                        v = P.a[rbase[i] + (long long)ci * P.acs + ((long long)yy * P.W + xx) * P.aps];
+                        v = P.a[rbase[i] + (long long)ci * P.acs + SW_GEMM_EXT_SRC(yy, xx) * P.aps];
                         if (P.isub) v = (v - sub) * P.imul;
                     }
                     av[i][e] = v;
@@ -235,6 +235,9 @@ __global__ __launch_bounds__(256) void sw_gemm_s3x_kernel(const GemmP P, const u
             if (P.act == ACT_GELU) x = 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
             else if (P.act == ACT_LRELU) x = x >= 0.f ? x : x * P.slope;
             const long long b = m / P.HW, p = m - b * P.HW;
+#if SW_GEMM_EXT
+            gemm_store_ext(P, x, b, p, n);
+#else
             if (P.res) x += P.res[b * P.rbs + p * P.rps + n];
             if (P.omode == O_TOK) {
                 P.y[b * P.ybs + p * P.yps + n] = x;
@@ -245,6 +248,7 @@ __global__ __launch_bounds__(256) void sw_gemm_s3x_kernel(const GemmP P, const u
             } else {
                 P.y[b * P.ybs + (long long)n * P.HW + p] = x / P.orange + P.omean[n];
             }
+#endif
         }
     }
 }
@@ -316,12 +320,13 @@ int set_math(SwBase* r, const char* net, int mode)
     return XSD_OK;
 }
 
-// The GEMM on its own (tests): see include/xsd.h, xsd_sw_test_gemm.
+// The GEMM on its own (tests): see include/xsd.h, xsd_sw_test_gemm.  With up2 (conv3 only, SW_GEMM_EXT) the conv runs over the nearest-2x
+// upsampling of the H x W input: 4 B H W output rows.
 int test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int conv3, int B, int H, int W, int cin, int N,
-              long long ldy, int act, float slope, int math, hipStream_t s)
+              long long ldy, int act, float slope, int math, hipStream_t s, bool up2 = false)
 {
     if (!dev_a || !dev_w || !dev_y) return rfail(XSD_ERR_ARG, "null argument");
-    if (B < 1 || H < 1 || W < 1 || cin < 1 || N < 1 || ldy < N || (long long)B * H * W > (1ll << 28) || cin > 65536 || N > 65536)
+    if (B < 1 || H < 1 || W < 1 || cin < 1 || N < 1 || ldy < N || (long long)B * H * W * (up2 ? 4 : 1) > (1ll << 28) || cin > 65536 || N > 65536)
         return rfail(XSD_ERR_ARG, "GEMM test: bad shape");
     if (act < ACT_NONE || act > ACT_LRELU) return rfail(XSD_ERR_ARG, "GEMM test: activation %d (0 none, 1 GELU, 2 LeakyReLU)", act);
     if (math != 0 && math != 3) return rfail(XSD_ERR_ARG, "GEMM test: the math modes are fp32 (0) and bf16x6 (3)");
@@ -342,7 +347,8 @@ int test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, flo
     }
     if (!e) {
         const long long rows = (long long)B * H * W;
-        GemmP p = conv3 ? gp_conv(dev_a, B, H, W, cin, (const float*)wp, N, dev_bias, dev_y, ldy)
+        GemmP p = up2   ? gp_conv_up2(dev_a, B, H, W, cin, (const float*)wp, N, dev_bias, dev_y, ldy)
+                : conv3 ? gp_conv(dev_a, B, H, W, cin, (const float*)wp, N, dev_bias, dev_y, ldy)
                         : gp_tok(dev_a, rows, cin, cin, (const float*)wp, N, dev_bias, dev_y, ldy);
         p.act = act; p.slope = slope;
         e = math == 3 ? gemm_s3x(s, p, (const unsigned short*)wp) : gemm(s, p);

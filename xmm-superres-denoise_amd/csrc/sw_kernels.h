@@ -1,4 +1,4 @@
-// sw_kernels.h -- the exact-fp32 kernels that the Swin-family networks (swinfir.hip, hat.hip) share, with their launch helpers.
+// sw_kernels.h -- the exact-fp32 kernels that the Swin-family networks (swinfir.hip, hat.hip, swinir.hip) share, with their launch helpers.
 //
 // Every product is an fp32 FMA on the fp32 matrix instruction v_mfma_f32_32x32x2_f32 (bitwise a k-ordered fmaf chain).  The GEMM's
 // fmaf chains are 16 long, their sums over K are carried in double, as are the LayerNorm statistics.  No float atomics anywhere and
@@ -62,7 +62,14 @@ constexpr int GAP = GM + 4;  // LDS row pitch of the A tile
 
 enum { A_TOK = 0, A_CONV3 = 1 };
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_LRELU = 2 };
-enum { O_TOK = 0, O_SHUFFLE = 1, O_NCHW = 2 };
+enum { O_TOK = 0, O_SHUFFLE = 1, O_NCHW = 2, O_SHUFFLE_NCHW = 3 };
+
+// The addressing that only SwinIR uses (GemmP's last fields: the nearest-2x source of a conv, an NCHW residual, cropped NCHW stores,
+// PixelShuffle straight into NCHW) is compiled into the GEMM kernels of a file that defines SW_GEMM_EXT as 1 before it includes this
+// header.  The other files' instances are built without it: the instruction streams of SwinFIR and HAT hold none of it.
+#ifndef SW_GEMM_EXT
+#define SW_GEMM_EXT 0
+#endif
 
 struct GemmP {
     int amode;
@@ -78,7 +85,44 @@ struct GemmP {
     float* y; long long ybs, yps;              // O_TOK: y[b ybs + p yps + n]; O_SHUFFLE: yps = N / r^2 channels of the r H x r W output
     int r;
     const float* omean; float orange;          // O_NCHW: y[b ybs + n HW + p] = v / orange + omean[n]
+    // SW_GEMM_EXT only; all zero = none of it
+    int up2;                                   // conv mode: the input is the nearest-2x upsampling of an (H / 2) x (W / 2) image that is never
+                                               // made: tap (yy, xx) of the H x W extent (which the zero padding is tested against) reads
+                                               // source pixel (yy >> 1, xx >> 1); abs is the stride of a SOURCE image
+    int rnchw;                                 // the residual is NCHW: res[b rbs + n HW + p]
+    int cH, cW;                                // O_NCHW: only rows < cH and columns < cW are stored, as a [N][cH][cW] image at b ybs.
+                                               // O_SHUFFLE_NCHW: PixelShuffle(r) of the N = r^2 channels-out columns, v / orange + omean[ch],
+                                               // into the [N / r^2][cH][cW] image at b ybs (the crop of the r H x r W result)
 };
+
+// SW_GEMM_EXT_SRC(yy, xx): the source pixel of tap (yy, xx) inside the image
+#if SW_GEMM_EXT
+#define SW_GEMM_EXT_SRC(yy, xx) (P.up2 ? (long long)((yy) >> 1) * (P.W >> 1) + ((xx) >> 1) : (long long)(yy) * P.W + (xx))
+
+// the residual add and the store of one result with the SwinIR addressing: the epilogue tail of both GEMM kernels of such a file
+__device__ __forceinline__ void gemm_store_ext(const GemmP& P, float x, long long b, long long p, int n)
+{
+    if (P.res) x += P.rnchw ? P.res[b * P.rbs + (long long)n * P.HW + p] : P.res[b * P.rbs + p * P.rps + n];
+    if (P.omode == O_TOK) {
+        P.y[b * P.ybs + p * P.yps + n] = x;
+    } else if (P.omode == O_SHUFFLE) {
+        const int r = P.r, ch = n / (r * r), rem = n - ch * r * r, ii = rem / r, jj = rem - ii * r;
+        const long long py = p / P.W, px = p - py * P.W;
+        P.y[b * P.ybs + ((py * r + ii) * ((long long)P.W * r) + px * r + jj) * P.yps + ch] = x;
+    } else if (P.omode == O_SHUFFLE_NCHW) {
+        const int r = P.r, ch = n / (r * r), rem = n - ch * r * r, ii = rem / r, jj = rem - ii * r;
+        const long long py = p / P.W, px = p - py * P.W, oy = py * r + ii, ox = px * r + jj;
+        if (oy < P.cH && ox < P.cW) P.y[b * P.ybs + ((long long)ch * P.cH + oy) * P.cW + ox] = x / P.orange + P.omean[ch];
+    } else if (P.cW) {
+        const long long py = p / P.W, px = p - py * P.W;
+        if (py < P.cH && px < P.cW) P.y[b * P.ybs + ((long long)n * P.cH + py) * P.cW + px] = x / P.orange + P.omean[n];
+    } else {
+        P.y[b * P.ybs + (long long)n * P.HW + p] = x / P.orange + P.omean[n];
+    }
+}
+#else
+#define SW_GEMM_EXT_SRC(yy, xx) ((long long)yy * P.W + xx)
+#endif
 
 __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
 {
@@ -121,7 +165,7 @@ __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
                 const int yy = ry[i] + dy, xx = rx[i] + dx;
                 float v = 0.f;
                 if (rok[i] && kok && yy >= 0 && yy < P.H && xx >= 0 && xx < P.W) {
-                    v = P.a[rbase[i] + (long long)ci * P.acs + ((long long)yy * P.W + xx) * P.aps];
+                    v = P.a[rbase[i] + (long long)ci * P.acs + SW_GEMM_EXT_SRC(yy, xx) * P.aps];
                     if (P.isub) v = (v - sub) * P.imul;
                 }
                 av[i] = v;
@@ -170,10 +214,19 @@ __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
         for (int v = 0; v < 16; ++v) {
             const long long m = m0 + 32 * wave + 8 * (v >> 2) + 4 * h2 + (v & 3);
             if (m >= M) continue;
+            // SW_GEMM_EXT: the bias joins the double sum, so the result is rounded to fp32 once.  The other instances keep their two
+            // roundings (sum, then + bias): their outputs stay what they were, bit for bit.
+#if SW_GEMM_EXT
+            float x = (float)((c ? d1[v] : d0[v]) + (double)bn);
+#else
             float x = (float)(c ? d1[v] : d0[v]) + bn;
+#endif
             if (P.act == ACT_GELU) x = 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
             else if (P.act == ACT_LRELU) x = x >= 0.f ? x : x * P.slope;
             const long long b = m / P.HW, p = m - b * P.HW;
+#if SW_GEMM_EXT
+            gemm_store_ext(P, x, b, p, n);
+#else
             if (P.res) x += P.res[b * P.rbs + p * P.rps + n];
             if (P.omode == O_TOK) {
                 P.y[b * P.ybs + p * P.yps + n] = x;
@@ -184,6 +237,7 @@ __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
             } else {
                 P.y[b * P.ybs + (long long)n * P.HW + p] = x / P.orange + P.omean[n];
             }
+#endif
         }
     }
 }
@@ -370,6 +424,15 @@ GemmP gp_conv(const float* x, int B, int H, int W, int cin, const float* w, int 
     return p;
 }
 
+// a 3x3 conv over the nearest-2x upsampling of B token-major images of H x W (SW_GEMM_EXT): output rows are the 2 H x 2 W pixels
+GemmP gp_conv_up2(const float* x, int B, int H, int W, int cin, const float* w, int N, const float* bias, float* y, long long ldy)
+{
+    GemmP p = gp_conv(x, B, 2 * H, 2 * W, cin, w, N, bias, y, ldy);
+    p.abs = (long long)H * W * cin;
+    p.up2 = 1;
+    return p;
+}
+
 hipError_t gemm(hipStream_t s, const GemmP& p)
 {
     const long long M = (long long)p.B * p.HW;
@@ -430,13 +493,14 @@ const char* upsampler_name(int u)
 }
 
 // the checks of the constructor arguments that both networks share, under the name `net` of the one that asks
+// (upscale 1, a head that does not enlarge, is SwinIR's alone: `upscale1`)
 template <class Cfg>
-int check_dims(const Cfg& c, const char* net)
+int check_dims(const Cfg& c, const char* net, bool upscale1 = false)
 {
     if (c.in_chans < 1 || c.in_chans > 64) return rfail(XSD_ERR_ARG, "%s: in_chans must be in [1, 64] (got %d)", net, c.in_chans);
     if (c.embed_dim < 2 || c.embed_dim > 4096) return rfail(XSD_ERR_ARG, "%s: embed_dim must be in [2, 4096] (got %d)", net, c.embed_dim);
     if (c.num_layers < 0 || c.num_layers > 16) return rfail(XSD_ERR_ARG, "%s: at most 16 layers (got %d)", net, c.num_layers);
-    if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
+    if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8 && !(upscale1 && c.upscale == 1))
         return rfail(XSD_ERR_ARG, "%s: upscale %d is not supported (2^n and 3, modules.py Upsample)", net, c.upscale);
     if (!(c.img_range > 0)) return rfail(XSD_ERR_ARG, "%s: img_range must be positive", net);
     if (!(c.qk_scale >= 0))
@@ -560,8 +624,34 @@ hipError_t mlp(hipStream_t s, const SwBase* r, float* X, float* O, long long M, 
     return gemm(s, r, p);
 }
 
-// conv_before_upsample + LeakyReLU(0.01), the PixelShuffle stages of Upsample, conv_last into NCHW x / img_range + mean
-hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, int in_chans, int upscale, float img_range)
+// one Swin block's weights in the flat buffer (modules.py SwinTransformerBlock / WindowAttention / Mlp) and its shift
+struct SBlk {
+    long long n1w, n1b, table, n2w, n2b;
+    Lin qkv, proj, fc1, fc2;
+    int shift;
+};
+
+// SwinTransformerBlock (modules.py:299-350) on the token rows of X: x += proj(attn(norm1(x))); x += fc2(gelu(fc1(norm2(x)))).  O is free.
+hipError_t swin_block(hipStream_t s, const SwBase* r, const SBlk& k, float* X, float* O, int B, int H, int W, int heads, float scale)
+{
+    const int E = r->E;
+    const long long M = (long long)B * H * W;
+    const float* wt = r->wt;
+    hipError_t e;
+    // norm1 into O (free until the attention writes it); a LayerNorm prologue inside the GEMM measured slower, DESIGN §12
+    if ((e = ln(s, X, O, PP(r, k.n1w), PP(r, k.n1b), M, E))) return e;
+    GemmP p = gp_tok(O, M, E, E, wt + k.qkv.t, 3 * E, PP(r, k.qkv.b), r->A, 3 * E);
+    if ((e = gemm(s, r, p))) return e;
+    if ((e = attention(s, r->A, O, r->params + k.table, B, H, W, E, heads, r->ws, k.shift, scale))) return e;
+    p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
+    p.res = X; p.rbs = 0; p.rps = E;
+    if ((e = gemm(s, r, p))) return e;
+    return mlp(s, r, X, O, M, k.n2w, k.n2b, k.fc1, k.fc2);
+}
+
+// conv_before_upsample + LeakyReLU(0.01), the PixelShuffle stages of Upsample, conv_last into NCHW x / img_range + mean.  With cH and
+// cW (SW_GEMM_EXT) only the top-left cH x cW of the result is stored, as an image of that size.
+hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, int in_chans, int upscale, float img_range, int cH = 0, int cW = 0)
 {
     const int B = r->B, nf = r->nfeat;
     GemmP p = gp_conv(X, B, r->H, r->W, r->E, r->wt + r->before.t, nf, PP(r, r->before.b), r->V, nf);
@@ -580,6 +670,7 @@ hipError_t tail(hipStream_t s, const SwBase* r, const float* X, float* dev_y, in
     }
     p = gp_conv(cur, B, h, w, nf, r->wt + r->last.t, in_chans, PP(r, r->last.b), dev_y, 0);
     p.omode = O_NCHW; p.ybs = (long long)in_chans * h * w; p.omean = r->mean; p.orange = img_range;
+    if (cW) { p.cH = cH; p.cW = cW; p.ybs = (long long)in_chans * cH * cW; }
     return gemm(s, r, p);
 }
 

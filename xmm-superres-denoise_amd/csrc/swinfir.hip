@@ -151,12 +151,6 @@ __global__ __launch_bounds__(256) void sw_fft_kernel(const FftP P)
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct SBlk {
-    long long n1w, n1b, table, n2w, n2b;
-    Lin qkv, proj, fc1, fc2;
-    int shift;
-};
-
 struct Layer {
     std::vector<SBlk> blks;
     int heads;
@@ -413,16 +407,7 @@ int xsd_swinfir_forward(xsd_swinfir* r, const float* dev_x, float* dev_y, int B,
         // the RSTB's input: its `+ x` (swinfir.py:214-216) adds it after the blocks and the conv
         SW(hipMemcpyAsync(r->R0, X, sizeof(float) * M * E, hipMemcpyDeviceToDevice, s));
         for (const SBlk& k : L.blks) {
-            // SwinTransformerBlock (modules.py:299-350): x += proj(attn(norm1(x))); x += fc2(gelu(fc1(norm2(x))))
-            // norm1 into O (free until the attention writes it); a LayerNorm prologue inside the GEMM measured slower, DESIGN §12
-            SW(ln(s, X, O, PP(r, k.n1w), PP(r, k.n1b), M, E));
-            GemmP p = gp_tok(O, M, E, E, wt + k.qkv.t, 3 * E, PP(r, k.qkv.b), r->A, 3 * E);
-            SW(gemm(s, r, p));
-            SW(attention(s, r->A, O, r->params + k.table, B, H, W, E, L.heads, r->ws, k.shift, attn_scale(c.qk_scale, E / L.heads)));
-            p = gp_tok(O, M, E, E, wt + k.proj.t, E, PP(r, k.proj.b), X, E);
-            p.res = X; p.rbs = 0; p.rps = E;
-            SW(gemm(s, r, p));
-            SW(mlp(s, r, X, O, M, k.n2w, k.n2b, k.fc1, k.fc2));
+            SW(swin_block(s, r, k, X, O, B, H, W, L.heads, attn_scale(c.qk_scale, E / L.heads)));      // sw_kernels.h
         }
         if (c.resi_connection == 0) {
             // RSTB tail x = SFB(x) + RSTB input (swinfir.py:103-117, :214-216); CAT = [S | F] as the row halves of the A buffer

@@ -38,6 +38,10 @@ class XsdSwinFIRConfig(ctypes.Structure):
                 ("img_range", ctypes.c_double)]
 
 
+class XsdSwinIRConfig(ctypes.Structure):      # the same fields as SwinFIR's; upsampler 0..3 and resi_connection 0 "1conv" / 1 "3conv"
+    _fields_ = list(XsdSwinFIRConfig._fields_)
+
+
 class XsdHATConfig(ctypes.Structure):
     _fields_ = [("img_size", ctypes.c_int32 * 2), ("patch_size", ctypes.c_int32 * 2), ("in_chans", ctypes.c_int32),
                 ("embed_dim", ctypes.c_int32), ("num_layers", ctypes.c_int32), ("depths", ctypes.c_int32 * 16),
@@ -137,6 +141,18 @@ def load():
     L.xsd_swinfir_get_math.argtypes = [vp]
     L.xsd_hat_set_math.argtypes = [vp, i32]
     L.xsd_hat_get_math.argtypes = [vp]
+    L.xsd_swinir_create.argtypes = [ctypes.POINTER(XsdSwinIRConfig), ctypes.POINTER(vp)]
+    L.xsd_swinir_destroy.argtypes = [vp]
+    L.xsd_swinir_destroy.restype = None
+    L.xsd_swinir_param_count.argtypes = [vp]
+    L.xsd_swinir_param_count.restype = i64
+    L.xsd_swinir_pack_weights.argtypes = [vp, fp, vp]
+    L.xsd_swinir_forward.argtypes = [vp, fp, fp, i32, i32, i32, vp]
+    L.xsd_swinir_out_size.argtypes = [vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.xsd_swinir_set_math.argtypes = [vp, i32]
+    L.xsd_swinir_get_math.argtypes = [vp]
+    L.xsd_swinir_test_pad.argtypes = [fp, fp, i32, i32, i32, i32, i32, ctypes.POINTER(f32), f32, vp]
+    L.xsd_swinir_test_nearest_conv.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, f32, i32, vp]
     L.xsd_sw_test_gemm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i64, i32, f32, i32, vp]
     L.xsd_hat_test_ocab.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     L.xsd_hat_test_channel_mean.argtypes = [fp, fp, i32, i64, i32, vp]
@@ -163,6 +179,8 @@ ABI_SYMBOLS = [
     "xsd_hat_create", "xsd_hat_destroy", "xsd_hat_param_count", "xsd_hat_pack_weights", "xsd_hat_forward", "xsd_hat_test_ocab",
     "xsd_hat_test_channel_mean", "xsd_hat_set_math", "xsd_hat_get_math",
     "xsd_sw_test_attention", "xsd_sw_test_layernorm", "xsd_hat_test_ca_combine",
+    "xsd_swinir_create", "xsd_swinir_destroy", "xsd_swinir_param_count", "xsd_swinir_pack_weights", "xsd_swinir_forward",
+    "xsd_swinir_out_size", "xsd_swinir_set_math", "xsd_swinir_get_math", "xsd_swinir_test_pad", "xsd_swinir_test_nearest_conv",
     "xsd_restormer_test_pw", "xsd_restormer_test_dw", "xsd_restormer_test_attention", "xsd_restormer_test_conv3",
 ]
 

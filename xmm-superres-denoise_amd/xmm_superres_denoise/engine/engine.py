@@ -368,6 +368,99 @@ class HATEngine(_ForwardEngine):
         self.in_chans, self.upscale = int(in_chans), int(upscale)
 
 
+class SwinIREngine(_ForwardEngine):
+    """One SwinIR engine per module per GPU (xsd_swinir_create / _destroy): forward only, any image size (the engine reflect-pads to
+    multiples of window_size and crops back)."""
+
+    UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
+    RESI = ("1conv", "3conv")
+    PREFIX = "xsd_swinir_"
+    NAME = "SwinIR"
+
+    def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
+                 qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
+                 resi_connection: str):
+        super().__init__()
+        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
+        if len(depths) > 16 or len(num_heads) < len(depths):
+            raise XsdError(f"SwinIR: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
+        if upsampler not in self.UPSAMPLERS:
+            raise XsdError(f"SwinIR: unknown upsampler {upsampler!r}: {self.UPSAMPLERS}")
+        cfg = _lib.XsdSwinIRConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
+                                   in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
+                                   depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
+                                   window_size=int(window_size), qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)),
+                                   patch_norm=int(bool(patch_norm)), upscale=int(upscale), upsampler=self.UPSAMPLERS.index(upsampler),
+                                   resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 2,
+                                   mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range))
+        self._create(cfg, in_chans, in_chans, upscale)
+        self.in_chans, self.upscale = int(in_chans), int(upscale)
+
+    def out_size(self, H: int, W: int) -> tuple[int, int]:
+        """(Ho, Wo) of forward's output for an H x W input (xsd_swinir_out_size): H upscale x W upscale for every head that enlarges;
+        raises XsdError for the sizes the forward refuses.  Host arithmetic: no device work."""
+        ho, wo = ctypes.c_int(), ctypes.c_int()
+        check(self.L.xsd_swinir_out_size(self.h, int(H), int(W), ctypes.byref(ho), ctypes.byref(wo)))
+        return ho.value, wo.value
+
+    @_on_engine_device
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        _require_cuda_f32(x, "x")
+        if x.dim() != 4 or x.shape[1] != self._cin:
+            raise XsdError(f"x must be [B,{self._cin},H,W] (got {tuple(x.shape)})")
+        B, _, H, W = x.shape
+        Ho, Wo = self.out_size(H, W)
+        y = torch.empty((B, self._cout, Ho, Wo), device=x.device, dtype=torch.float32)
+        check(self.L.xsd_swinir_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
+        return y
+
+
+@_on_tensor_device
+def swinir_pad(x: torch.Tensor, ws: int, mean=None, img_range: float = 1.0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """check_image_size and the input affine of SwinIR on their own (include/xsd.h: xsd_swinir_test_pad): x [B, C, H, W] ->
+    (F.pad(x, (0, pw, 0, ph), "reflect") - mean) * img_range with H + ph and W + pw the next multiples of ws; mean: C numbers or None."""
+    _require_cuda_f32(x, "x")
+    if x.dim() != 4:
+        raise XsdError(f"x {tuple(x.shape)} is not [B, C, H, W]")
+    B, C, H, W = (int(v) for v in x.shape)
+    ws = int(ws)
+    if ws < 1:
+        raise XsdError(f"window size {ws} must be positive")
+    shape = (B, C, H + (ws - H % ws) % ws, W + (ws - W % ws) % ws)
+    out = _out_like(out, shape, x.device, "out")
+    m = None
+    if mean is not None:
+        mean = [float(v) for v in mean]
+        if len(mean) != C:
+            raise XsdError(f"mean has {len(mean)} entries for {C} channels")
+        m = (ctypes.c_float * C)(*mean)
+    check(_lib.load().xsd_swinir_test_pad(x.data_ptr(), out.data_ptr(), B, C, H, W, ws, m, float(img_range), _stream_ptr(x.device)))
+    return out
+
+
+@_on_tensor_device
+def swinir_nearest_conv(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, slope: float = 0.2, math: str = "fp32",
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """lrelu(conv3x3(nearest2x(a))) of SwinIR's "nearest+conv" head on its own (include/xsd.h: xsd_swinir_test_nearest_conv): a [B, H, W, cin]
+    token-major, w [N, cin, 3, 3] -> [B, 2 H, 2 W, N] token-major; the upsampled image is never stored."""
+    _require_cuda_f32(a, "a")
+    _require_cuda_f32(w, "w")
+    if a.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (a.shape[3], 3, 3):
+        raise XsdError(f"a {tuple(a.shape)} and w {tuple(w.shape)} are not [B, H, W, cin] and [N, cin, 3, 3]")
+    if math not in SW_MATH:
+        raise XsdError(f"unknown math mode {math!r}: the modes are {sorted(SW_MATH)}")
+    B, H, W, cin = (int(v) for v in a.shape)
+    N = int(w.shape[0])
+    if bias is not None:
+        _require_cuda_f32(bias, "bias")
+        if bias.numel() != N:
+            raise XsdError(f"bias has {bias.numel()} elements for {N} outputs")
+    out = _out_like(out, (B, 2 * H, 2 * W, N), a.device, "out")
+    check(_lib.load().xsd_swinir_test_nearest_conv(a.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), B, H, W, cin, N, float(slope),
+                                                   SW_MATH[math], _stream_ptr(a.device)))
+    return out
+
+
 @_on_tensor_device
 def hat_ocab_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, heads: int, ws: int, ow: int, scale: float) -> torch.Tensor:
     """The OCAB's attention on its own (include/xsd.h: xsd_hat_test_ocab): qkv [B, H W, 3 C] token rows (the qkv Linear's output), table

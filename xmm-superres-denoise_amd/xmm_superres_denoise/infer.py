@@ -148,10 +148,26 @@ def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, d
     return model.to(device)
 
 
+def load_swinir(checkpoint: str, device="cuda:0", math: str | None = None, **ctor_kwargs):
+    """A bare `SwinIR` module (models/modules/swinir.py) built with `ctor_kwargs` -- the reference's constructor arguments -- holding the
+    weights of a checkpoint in the reference's key names, with or without Lightning's `model.` prefix (train.load_checkpoint), on `device`.
+    The reference has no factory entry and no models.toml name for SwinIR, so `load_model` does not know it; infer_file takes the module
+    as it is.  `math`: 'fp32' or 'bf16x6' (SwinIR.set_math); None leaves the default."""
+    from types import SimpleNamespace
+
+    from xmm_superres_denoise.models import SwinIR
+    from xmm_superres_denoise.train import load_checkpoint
+    module = SwinIR(**ctor_kwargs)
+    load_checkpoint(checkpoint, SimpleNamespace(model=module))
+    if math is not None:
+        module.set_math(math)
+    return module.to(device)
+
+
 @torch.no_grad()
 def infer_file(fits_path, model, det_mask: torch.Tensor | None, out_dir, lr_res: int = 416, lr_max: float = 0.0022336,
                hr_max: float = 0.0005584, stretch: str = "sqrt", device="cuda:0", write_input: bool = True):
-    """Run one det-xy image through `model` (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, HAT, or a `Model` of any of them, on `device`).  Returns (prediction [Hout,Wout] in
+    """Run one det-xy image through `model` (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, HAT, SwinIR, or a `Model` of any of them, on `device`).  Returns (prediction [Hout,Wout] in
     physical units, output path).  Mirrors run_inference_on_file.py:127-199 without the exposure bookkeeping against SAS."""
     from xmm_superres_denoise.engine import compose_input, normalize
     data, hdr = read_fits(fits_path)

@@ -3,3 +3,4 @@ from .modules.generator_rrdb import GeneratorRRDB_DN, GeneratorRRDB_SR  # noqa: 
 from .modules.hat import HAT  # noqa: F401
 from .modules.restormer import Restormer  # noqa: F401
 from .modules.swinfir import SwinFIR  # noqa: F401
+from .modules.swinir import SwinIR  # noqa: F401
