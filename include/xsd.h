@@ -258,7 +258,7 @@ typedef struct xsd_restormer_config {   /* Restormer.__init__ arguments (restorm
     int32_t dim;                   /* even, 2..1024 (Downsample halves it, :188) */
     int32_t num_blocks[4];         /* 0..64 each */
     int32_t num_refinement_blocks; /* 0..64 */
-    int32_t heads[4];              /* heads[l] divides dim * 2^l (heads[0] also 2 dim) into at most 64 channels per head */
+    int32_t heads[4];              /* heads[l] divides dim * 2^l (heads[0] also 2 dim) into at most 128 channels per head */
     int32_t bias;                  /* 0/1: conv biases */
     int32_t layernorm_bias_free;   /* 0 = "WithBias", 1 = "BiasFree" (:61-73) */
     int32_t dual_pixel_task;       /* must be 0 (refused) */
@@ -292,9 +292,13 @@ int xsd_restormer_test_dw(const float* dev_x, const float* dev_w, const float* d
                           void* stream);
 /* The channel attention behind the depthwise conv (restormer.py:126-139): qkv [B][3 C][HW], temperature [heads], dev_wpo [C][C] and
  * dev_bpo [C] or NULL project_out as stored; x [B][C][HW] in place: x += project_out(softmax(normalize(q) normalize(k)^T temperature) v).
- * heads divides C into at most 64 channels per head, C <= 8192. */
+ * heads divides C into at most 64 channels per head, C <= 8192: what the forward runs up to that width. */
 int xsd_restormer_test_attention(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x, int B,
                                  int C, int heads, int64_t HW, void* stream);
+/* The same contract through the wide kernels, which the forward runs from 65 to 128 channels per head: here at any width in [1, 128]
+ * (up to 64 the result is bitwise that of xsd_restormer_test_attention). */
+int xsd_restormer_test_attention_wide(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x,
+                                      int B, int C, int heads, int64_t HW, void* stream);
 /* The dense 3x3 conv, zero padding 1: x [B][cin][H][W], dev_w [cout][cin][3][3], dev_bias [cout] or NULL, any H, W >= 1.
  * mode 0: y [B][cout][H][W] (+ dev_skip [B][cout][H][W] unless NULL); mode 1: y = PixelUnshuffle(2) of it, [B][4 cout][H/2][W/2], H and W
  * even; mode 2: y = PixelShuffle(2) of it, [B][cout/4][2 H][2 W], cout a multiple of 4.  dev_skip must be NULL in modes 1 and 2. */

@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Restormer forward speed on the MI355X: the engine (csrc/restormer.hip) against torch eager fp32 running the float64-oracle's
-restatement (tests/golden/restormer_torch.py) in fp32 on the same device, dim = 24 (models.toml:58-64), 416 x 416 tiles.
+restatement (tests/golden/restormer_torch.py) in fp32 on the same device, 416 x 416 tiles; --dim 24 (the default: models.toml:58-64, 1 -> 1
+channels) or any other width, of which 48 is the published network (3 -> 3 channels, 96 channels per head at decoder level 1: the wide
+channel-attention kernels).
 
-  python tools/restormer_speed.py time [--batches 1,4,16] [--iters 20]      one JSON line per batch: images/s of both
+  python tools/restormer_speed.py time [--dim 24] [--batches 1,4,16] [--iters 20] [--repeats 1]
+                                                                     one JSON line per batch: images/s of both; with --repeats R
+                                                                     the median of R timings of --iters forwards, and [min, max]
+  python tools/restormer_speed.py hooks [--shape 4,64,1,173056] [--iters 10] [--repeats 5]
+                                                                     the channel attention alone through the narrow and the wide
+                                                                     test hook (allocation, transpose and sync included in both)
   python tools/restormer_speed.py profile --batch 4 [--iters 5]             engine forwards only (run under rocprofv3 --kernel-trace --stats)
   python tools/restormer_speed.py roof <kernel_stats.csv | results.db> --batch 4 --iters N [--csv-out F]
                                                                      per-kernel time, achieved bytes/s against the HBM roof and
@@ -31,11 +38,17 @@ FP32_PEAK = 157.3e12                           # fp32 matrix peak (FLOP/s), the 
 CFG = dict(inp_channels=1, out_channels=1, dim=24)
 
 
+def cfg_of(dim: int) -> dict:
+    """the XMM configuration at `dim` (1 -> 1 channels); dim 48 is Restormer() as published, 3 -> 3 channels"""
+    return {} if dim == 48 else dict(CFG, dim=dim)
+
+
 def counts(B: int, H: int, W: int, cfg=CFG) -> dict:
     """algorithmic {kernel: [launches, bytes, flop]} of one engine forward"""
     c = gr.full_cfg(**cfg)
     d, f, heads, nb = c["dim"], c["ffn_expansion_factor"], c["heads"], c["num_blocks"]
-    out = {k: [0, 0.0, 0.0] for k in ("rst_pw_kernel", "rst_dw_kernel", "rst_gram_kernel", "rst_attn_kernel", "rst_conv3_kernel")}
+    out = {k: [0, 0.0, 0.0] for k in ("rst_pw_kernel", "rst_dw_kernel", "rst_gram_kernel", "rst_attn_kernel", "rst_wgram_kernel",
+                                      "rst_wsoftmax_kernel", "rst_wfold_kernel", "rst_conv3_kernel")}
 
     def add(k, nbytes, flop):
         out[k][0] += 1
@@ -46,8 +59,17 @@ def counts(B: int, H: int, W: int, cfg=CFG) -> dict:
         hid, ch, n = int(C * f), C // h, B * HW
         add("rst_pw_kernel", (C + 3 * C) * n, 2.0 * C * 3 * C * n)                  # LayerNorm + qkv
         add("rst_dw_kernel", 6 * C * n, 18.0 * 3 * C * n)                            # qkv_dwconv
-        add("rst_gram_kernel", 2 * C * n, 2.0 * (C * ch + 2 * C) * n)                # q k^T and the row norms
-        add("rst_attn_kernel", 2 * B * h * (ch * ch + 2 * ch) * -(-HW // 1024) + B * C * C, B * (2.0 * C * C * ch))   # double partials in
+        part = 2 * B * h * (ch * ch + 2 * ch) * -(-HW // 1024)                       # the double partials, in floats
+        if ch <= 64:
+            add("rst_gram_kernel", 2 * C * n, 2.0 * (C * ch + 2 * C) * n)            # q k^T and the row norms
+            add("rst_attn_kernel", part + B * C * C, B * (2.0 * C * C * ch))         # double partials in
+        else:
+            # the Gram in 64 x 64 tiles: every tile row reads its q rows once per tile column and the other way round, so q and k are
+            # read ceil(ch / 64) times; the FLOP are those of the entries inside the head (rows past it are skipped in groups of 16)
+            nt = -(-ch // 64)
+            add("rst_wgram_kernel", nt * 2 * C * n + part, 2.0 * (C * ch + 2 * C) * n)
+            add("rst_wsoftmax_kernel", part + B * C * ch, B * 10.0 * C * ch)
+            add("rst_wfold_kernel", B * (C * ch + 2 * C * C), B * (2.0 * C * C * ch))
         add("rst_pw_kernel", 3 * C * n, 2.0 * C * C * n)                             # (W_po attn) v + residual
         add("rst_pw_kernel", (C + 2 * hid) * n, 2.0 * C * 2 * hid * n)               # LayerNorm + project_in
         add("rst_dw_kernel", 3 * hid * n, (36.0 * hid + 10.0 * hid) * n)             # dwconv + gelu gate
@@ -77,6 +99,12 @@ def counts(B: int, H: int, W: int, cfg=CFG) -> dict:
     return out
 
 
+def _stat(ts):
+    ts = sorted(ts)
+    n = len(ts)
+    return (ts[n // 2] if n % 2 else 0.5 * (ts[n // 2 - 1] + ts[n // 2])), ts[0], ts[-1]
+
+
 def _time(fn, iters):
     import torch
     fn()
@@ -94,32 +122,61 @@ def cmd_time(a):
     import torch
     import restormer_torch as rt
     from xmm_superres_denoise.models import Restormer
-    state = gr.make_state(CFG, 2024)
-    m = Restormer(**gr.full_cfg(**CFG))
+    cfg = cfg_of(a.dim)
+    full = gr.full_cfg(**cfg)
+    state = gr.make_state(cfg, 2024)
+    m = Restormer(**full)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
     m = m.cuda()
     sd = {k: torch.from_numpy(v).cuda() for k, v in state.items()}
-    full = gr.full_cfg(**CFG)
     for B in [int(b) for b in a.batches.split(",")]:
-        x = torch.from_numpy(gr.make_input((B, 1, a.size, a.size), 7)).cuda()
+        x = torch.from_numpy(gr.make_input((B, full["inp_channels"], a.size, a.size), 7)).cuda()
         with torch.no_grad():
             for _ in range(2):          # warm-up: workspace plan, code objects, library algorithm choices
                 m(x)
                 rt.restormer_forward(sd, x, **full)
-            t_eng = _time(lambda: m(x), a.iters)
-            t_eager = _time(lambda: rt.restormer_forward(sd, x, **full), a.iters)
+            t_engs = [_time(lambda: m(x), a.iters) for _ in range(a.repeats)]
+            t_eagers = [_time(lambda: rt.restormer_forward(sd, x, **full), a.iters) for _ in range(a.repeats)]
             dmax = float((m(x) - rt.restormer_forward(sd, x, **full)).abs().max())
-        print(json.dumps({"batch": B, "size": a.size, "iters": a.iters, "engine_ms": round(t_eng * 1e3, 3),
-                          "engine_images_per_s": round(B / t_eng, 2), "torch_eager_fp32_ms": round(t_eager * 1e3, 3),
-                          "torch_eager_fp32_images_per_s": round(B / t_eager, 2), "engine_over_eager": round(t_eager / t_eng, 3),
-                          "max_abs_diff": dmax, "device": torch.cuda.get_device_name(0)}), flush=True)
+        (t_eng, e_lo, e_hi), (t_eager, g_lo, g_hi) = _stat(t_engs), _stat(t_eagers)
+        line = {"batch": B, "size": a.size, "iters": a.iters, "engine_ms": round(t_eng * 1e3, 3),
+                "engine_images_per_s": round(B / t_eng, 2), "torch_eager_fp32_ms": round(t_eager * 1e3, 3),
+                "torch_eager_fp32_images_per_s": round(B / t_eager, 2), "engine_over_eager": round(t_eager / t_eng, 3),
+                "max_abs_diff": dmax, "device": torch.cuda.get_device_name(0)}
+        if a.dim != 24 or a.repeats != 1:
+            line.update({"dim": a.dim, "repeats": a.repeats, "engine_ms_min_max": [round(e_lo * 1e3, 3), round(e_hi * 1e3, 3)],
+                         "torch_eager_fp32_ms_min_max": [round(g_lo * 1e3, 3), round(g_hi * 1e3, 3)]})
+        print(json.dumps(line), flush=True)
+
+
+def cmd_hooks(a):
+    """the channel attention alone at one shape both paths take (at most 64 channels per head), through the two test hooks"""
+    import torch
+    from xmm_superres_denoise.engine import restormer_channel_attention, restormer_channel_attention_wide
+    B, C, heads, HW = (int(v) for v in a.shape.split(","))
+    g = torch.Generator().manual_seed(1)
+    qkv = torch.randn(B, 3 * C, HW, generator=g).cuda()
+    temp = (torch.rand(heads, generator=g) + 0.5).cuda()
+    wpo = ((torch.rand(C, C, generator=g) * 2 - 1) / C ** 0.5).cuda()
+    x0 = torch.randn(B, C, HW, generator=g).cuda()
+    out, ts = {}, {}
+    for name, fn in (("narrow", restormer_channel_attention), ("wide", restormer_channel_attention_wide)):
+        x = x0.clone()
+        out[name] = fn(qkv, temp, wpo, None, x0.clone(), heads)
+        ts[name] = _stat([_time(lambda: fn(qkv, temp, wpo, None, x, heads), a.iters) for _ in range(a.repeats)])
+    print(json.dumps({"hooks": [B, C, heads, HW], "iters": a.iters, "repeats": a.repeats,
+                      "narrow_ms": round(ts["narrow"][0] * 1e3, 3), "narrow_ms_min_max": [round(v * 1e3, 3) for v in ts["narrow"][1:]],
+                      "wide_ms": round(ts["wide"][0] * 1e3, 3), "wide_ms_min_max": [round(v * 1e3, 3) for v in ts["wide"][1:]],
+                      "wide_over_narrow": round(ts["wide"][0] / ts["narrow"][0], 3), "bitwise_equal": bool(torch.equal(out["narrow"], out["wide"])),
+                      "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
 def cmd_profile(a):
     import torch
     from xmm_superres_denoise.models import Restormer
-    m = Restormer(**gr.full_cfg(**CFG)).cuda()
-    x = torch.from_numpy(gr.make_input((a.batch, 1, a.size, a.size), 7)).cuda()
+    full = gr.full_cfg(**cfg_of(a.dim))
+    m = Restormer(**full).cuda()
+    x = torch.from_numpy(gr.make_input((a.batch, full["inp_channels"], a.size, a.size), 7)).cuda()
     with torch.no_grad():
         m(x)            # first forward: plan + pack (the stats file counts it: `roof` takes iters + 1 forwards)
         for _ in range(a.iters):
@@ -140,7 +197,7 @@ def stats_rows(path):
 
 
 def cmd_roof(a):
-    per = counts(a.batch, a.size, a.size)
+    per = counts(a.batch, a.size, a.size, cfg_of(a.dim))
     n_fwd = a.iters + 1
     rows = stats_rows(a.stats)
     if a.csv_out:
@@ -169,6 +226,11 @@ def main():
     t.add_argument("--batches", default="1,4,16")
     t.add_argument("--iters", type=int, default=10)
     t.add_argument("--size", type=int, default=416)
+    t.add_argument("--repeats", type=int, default=1, help="timings of --iters forwards each: the median and [min, max] are reported")
+    h = sub.add_parser("hooks")
+    h.add_argument("--shape", default="4,64,1,173056", help="B,C,heads,HW with at most 64 channels per head")
+    h.add_argument("--iters", type=int, default=10)
+    h.add_argument("--repeats", type=int, default=5)
     p = sub.add_parser("profile")
     p.add_argument("--batch", type=int, default=4)
     p.add_argument("--iters", type=int, default=5)
@@ -179,8 +241,10 @@ def main():
     r.add_argument("--iters", type=int, default=5)
     r.add_argument("--size", type=int, default=416)
     r.add_argument("--csv-out", default=None, help="also write the kernel stats as CSV")
+    for q in (t, p, r):
+        q.add_argument("--dim", type=int, default=24, help="24: the XMM configuration; 48: Restormer() as published (3 -> 3 channels)")
     a = ap.parse_args()
-    {"time": cmd_time, "profile": cmd_profile, "roof": cmd_roof}[a.cmd](a)
+    {"time": cmd_time, "hooks": cmd_hooks, "profile": cmd_profile, "roof": cmd_roof}[a.cmd](a)
 
 
 if __name__ == "__main__":

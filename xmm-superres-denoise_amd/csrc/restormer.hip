@@ -21,6 +21,10 @@
 //   rst_attn_kernel    per image and head: combine the ranges (double, fixed order), F.normalize (eps 1e-12) as a division of the
 //                      Gram by the two norms, x temperature, softmax over the last dim, then fold project_out into it:
 //                      project_out(attn @ v) = (W_po blockdiag(attn_h)) v, i.e. a per-image C x C 1x1 conv applied to v.
+//   rst_wgram_kernel, rst_wsoftmax_kernel, rst_wfold_kernel
+//                      the same channel attention from 65 to 128 channels per head (the published dim 48 runs 96 on one head at
+//                      decoder level 1): the Gram tiled over the grid, the softmax and the fold as kernels of their own; the
+//                      arithmetic of the two kernels above entry by entry.
 //   rst_conv3_kernel   dense 3x3 conv (patch_embed :160, Downsample / Upsample bodies, output :366; summed in double) with plain,
 //                      PixelUnshuffle(2) or PixelShuffle(2) store and the `+ inp_img` skip (:404).
 #include <hip/hip_runtime.h>
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(256) void rst_dw_kernel(const DwP P)
     P.y[(long long)b * P.ybs + (long long)c * HW + p] = v;
 }
 
-constexpr int AT_MAXCH = 64;                                          // channels per head
+constexpr int AT_MAXCH = 64;                                          // channels per head (rst_gram_kernel / rst_attn_kernel)
 constexpr int AT_PX = 64;                                             // pixels per LDS round
 constexpr int AT_MAXE = (AT_MAXCH * AT_MAXCH + 2 * AT_MAXCH + 255) / 256;   // entries per thread
 
@@ -289,6 +293,174 @@ __global__ __launch_bounds__(256) void rst_attn_kernel(const AttnP P)
         for (int i = 0; i < ch; ++i) s = fma((double)P.wpo_t[(long long)(h * ch + i) * C + co], (double)A[i][j], s);
         mb[(long long)(h * ch + j) * C + co] = (float)s;
     }
+}
+
+// ---- the wide path: 65 to 128 channels per head (the kernels take any ch in [1, 128]) -----------------------------------------------
+// The same arithmetic, entry by entry, as the two kernels above (on a width both take, the outputs are bitwise equal), with the Gram
+// tiled over the grid instead of held whole by one workgroup: a workgroup owns a 64 x 64 tile of q k^T over one pixel range, a thread a
+// 4 x 4 block of it in registers.  The softmax and the fold are kernels of their own, attn in an fp32 scratch between them.
+constexpr int WD_MAXCH = 128;                                         // channels per head
+constexpr int WD_T = 64;                                              // Gram tile: 64 q rows x 64 k rows
+constexpr int WD_LD = AT_PX + 4;                                      // LDS row stride: float4 reads, 16 rows on 16 different 16-B slots
+constexpr int WS_ROWS = 8;                                            // attn rows per softmax workgroup
+
+__global__ __launch_bounds__(256) void rst_wgram_kernel(const GramP P)
+{
+    __shared__ __attribute__((aligned(16))) float qs[WD_T][WD_LD], ks[WD_T][WD_LD];
+    const int ch = P.ch, tid = threadIdx.x, nt = (ch + WD_T - 1) / WD_T, heads = gridDim.y / (nt * nt);
+    const int s = blockIdx.x, h = blockIdx.y / (nt * nt), tile = blockIdx.y % (nt * nt), b = blockIdx.z;
+    const int i0 = (tile / nt) * WD_T, j0 = (tile % nt) * WD_T;       // first q row / k row of the tile
+    const int ni = min(WD_T, ch - i0), nj = min(WD_T, ch - j0);       // rows of it inside the head
+    const int nr = (ni + 15) / 16, ns = (nj + 15) / 16;               // 16-row groups with a row inside (the same for every thread)
+    const int ti = tid >> 4, tj = tid & 15;                           // the thread's entries: q rows ti + 16 r, k rows tj + 16 s
+    const int E = ch * ch + 2 * ch;
+    const float* qb = P.qkv + (long long)b * P.bs + (long long)h * ch * P.HW;
+    const float* kb = qb + (long long)P.C * P.HW;
+    const long long pb = (long long)s * P.chunk, pe = min(P.HW, pb + P.chunk);
+    // the tiles of the first tile column carry the q norms of their rows, those of the first tile row the k norms: waves 0 and 1
+    const float* nrow = nullptr;
+    if (tile % nt == 0 && tid < ni) nrow = qs[tid];
+    else if (tile / nt == 0 && tid >= 64 && tid - 64 < nj) nrow = ks[tid - 64];
+    double acc[4][4], nacc = 0.0;      // fp32 FMA chain over one 64-pixel round, rounds summed in double
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
+    for (long long r0 = pb; r0 < pe; r0 += AT_PX) {
+        __syncthreads();
+        for (int i = tid; i < WD_T * AT_PX; i += 256) {
+            const int c = i / AT_PX, px = i % AT_PX;
+            const long long pp = r0 + px;
+            const bool ok = pp < pe;
+            qs[c][px] = (ok && c < ni) ? qb[(long long)(i0 + c) * P.HW + pp] : 0.f;
+            ks[c][px] = (ok && c < nj) ? kb[(long long)(j0 + c) * P.HW + pp] : 0.f;
+        }
+        __syncthreads();
+        float t[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[r][c] = 0.f;
+        for (int px = 0; px < AT_PX; px += 4) {
+            float4 kv[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (c < ns) kv[c] = *reinterpret_cast<const float4*>(&ks[tj + 16 * c][px]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (r >= nr) break;
+                const float4 qv = *reinterpret_cast<const float4*>(&qs[ti + 16 * r][px]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c >= ns) break;
+                    float v = t[r][c];
+                    v = fmaf(qv.x, kv[c].x, v);
+                    v = fmaf(qv.y, kv[c].y, v);
+                    v = fmaf(qv.z, kv[c].z, v);
+                    v = fmaf(qv.w, kv[c].w, v);
+                    t[r][c] = v;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[r][c] += (double)t[r][c];
+        if (nrow) {
+            float v = 0.f;
+            for (int px = 0; px < AT_PX; px += 4) {
+                const float4 a = *reinterpret_cast<const float4*>(&nrow[px]);
+                v = fmaf(a.x, a.x, v);
+                v = fmaf(a.y, a.y, v);
+                v = fmaf(a.z, a.z, v);
+                v = fmaf(a.w, a.w, v);
+            }
+            nacc += (double)v;
+        }
+    }
+    double* out = P.part + (((long long)b * heads + h) * P.nsplit + s) * E;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int i = ti + 16 * r, j = tj + 16 * c;
+            if (i < ni && j < nj) out[(i0 + i) * ch + j0 + j] = acc[r][c];
+        }
+    if (nrow) out[ch * ch + (tid < 64 ? i0 + tid : ch + j0 + tid - 64)] = nacc;
+}
+
+struct WSoftP {
+    const double* part; int nsplit;
+    const float* temp;                   // [heads]
+    float* attn; int ch;                 // [B][heads][ch][ch]
+};
+
+// WS_ROWS rows of one head's attn: the ranges combined (double, ascending), the Gram divided by the two clamped norms, x temperature, the
+// softmax of each row.  The logits and the exponentials are computed entry by entry in parallel; the running maximum and the
+// denominator of a row are taken by one thread over ascending j, as rst_attn_kernel takes them.
+__global__ __launch_bounds__(256) void rst_wsoftmax_kernel(const WSoftP P)
+{
+    __shared__ double l[WS_ROWS][WD_MAXCH], nk[WD_MAXCH], nq[WS_ROWS], mx_s[WS_ROWS], den_s[WS_ROWS];
+    const int i0 = blockIdx.x * WS_ROWS, h = blockIdx.y, b = blockIdx.z, heads = gridDim.y, ch = P.ch, tid = threadIdx.x;
+    const int rows = min(WS_ROWS, ch - i0), E = ch * ch + 2 * ch;
+    const double* pb = P.part + ((long long)b * heads + h) * P.nsplit * E;
+    for (int e = tid; e < rows * ch + ch + rows; e += 256) {
+        const int r = e / ch, j = e % ch;                  // r == rows: the k norms; past them: the q norms of the rows
+        const int src = e < rows * ch ? (i0 + r) * ch + j : e < rows * ch + ch ? ch * ch + ch + j : ch * ch + i0 + (e - rows * ch - ch);
+        double s = 0.0;
+        for (int k = 0; k < P.nsplit; ++k) s += pb[(long long)k * E + src];
+        if (e < rows * ch) l[r][j] = s;
+        else if (e < rows * ch + ch) nk[j] = fmax(sqrt(s), 1e-12);
+        else nq[e - rows * ch - ch] = fmax(sqrt(s), 1e-12);
+    }
+    __syncthreads();
+    const double t = (double)P.temp[h];
+    for (int e = tid; e < rows * ch; e += 256) {
+        const int r = e / ch, j = e % ch;
+        l[r][j] = l[r][j] / (nq[r] * nk[j]) * t;
+    }
+    __syncthreads();
+    if (tid < rows) {
+        double mx = -INFINITY;
+        for (int j = 0; j < ch; ++j) mx = fmax(mx, l[tid][j]);
+        mx_s[tid] = mx;
+    }
+    __syncthreads();
+    for (int e = tid; e < rows * ch; e += 256) {
+        const int r = e / ch, j = e % ch;
+        l[r][j] = exp(l[r][j] - mx_s[r]);
+    }
+    __syncthreads();
+    if (tid < rows) {
+        double den = 0.0;
+        for (int j = 0; j < ch; ++j) den += l[tid][j];
+        den_s[tid] = den;
+    }
+    __syncthreads();
+    float* ab = P.attn + (((long long)b * heads + h) * ch + i0) * ch;
+    for (int e = tid; e < rows * ch; e += 256) {
+        const int r = e / ch, j = e % ch;
+        ab[r * ch + j] = (float)(l[r][j] / den_s[r]);
+    }
+}
+
+struct WFoldP {
+    const float* attn;                   // [B][heads][ch][ch]
+    const float* wpo_t;                  // project_out weight, packed [C][C] = [ci][co]
+    float* mt; int C, ch;                // per-image folded matrix, [B][C][C] = [ci][co]
+};
+
+// M[co][h ch + j] = sum_i W_po[co][h ch + i] attn[i][j] (double fma over ascending i), stored transposed: mt[b][h ch + j][co]
+__global__ __launch_bounds__(256) void rst_wfold_kernel(const WFoldP P)
+{
+    const int h = blockIdx.y, b = blockIdx.z, heads = gridDim.y, ch = P.ch, C = P.C;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= ch * C) return;
+    const int j = e / C, co = e % C;
+    const float* ab = P.attn + ((long long)b * heads + h) * ch * ch;
+    double s = 0.0;
+    for (int i = 0; i < ch; ++i) s = fma((double)P.wpo_t[(long long)(h * ch + i) * C + co], (double)ab[i * ch + j], s);
+    P.mt[(long long)b * C * C + (long long)(h * ch + j) * C + co] = (float)s;
 }
 
 constexpr int C3T = 16;              // 16 x 16 pixel tile per workgroup
@@ -399,7 +571,7 @@ struct xsd_restormer {
     char* ws = nullptr;
     size_t ws_bytes = 0;
     float *slab1 = nullptr, *slab2 = nullptr, *dec2b = nullptr, *slab3 = nullptr, *dec3b = nullptr, *latb = nullptr;
-    float *Ta = nullptr, *Tb = nullptr, *part = nullptr, *mt = nullptr;
+    float *Ta = nullptr, *Tb = nullptr, *part = nullptr, *mt = nullptr, *attn = nullptr;
 
     ~xsd_restormer()
     {
@@ -501,12 +673,33 @@ hipError_t dw(hipStream_t s, const float* x, long long xbs, const float* w, cons
     return hipGetLastError();
 }
 
+// the same through the wide kernels (any ch in [1, 128]): the Gram tiled over pixel range x Gram tile x head x image, attn [B][heads][ch][ch]
+// in `attn` between the softmax and the fold
+hipError_t attention_wide(hipStream_t s, const float* qkv, long long qbs, const float* temp, const float* wpo_t, const float* bpo, double* part,
+                          float* attn, float* mt, float* X, long long xbs, int C, int heads, long long HW, int B)
+{
+    const int nsplit = nsplit_of(HW, GRAM_CHUNK), ch = C / heads, nt = (ch + WD_T - 1) / WD_T;
+    hipError_t e;
+    GramP p{qkv, qbs, C, ch, HW, GRAM_CHUNK, nsplit, part};
+    hipLaunchKernelGGL(rst_wgram_kernel, dim3((unsigned)nsplit, (unsigned)(heads * nt * nt), (unsigned)B), dim3(256), 0, s, p);
+    if ((e = hipGetLastError())) return e;
+    WSoftP a{part, nsplit, temp, attn, ch};
+    hipLaunchKernelGGL(rst_wsoftmax_kernel, dim3((unsigned)((ch + WS_ROWS - 1) / WS_ROWS), (unsigned)heads, (unsigned)B), dim3(256), 0, s, a);
+    if ((e = hipGetLastError())) return e;
+    WFoldP f{attn, wpo_t, mt, C, ch};
+    hipLaunchKernelGGL(rst_wfold_kernel, dim3((unsigned)((ch * C + 255) / 256), (unsigned)heads, (unsigned)B), dim3(256), 0, s, f);
+    if ((e = hipGetLastError())) return e;
+    return pw(s, qkv + 2 * C * HW, qbs, C, nullptr, nullptr, 0, mt, (long long)C * C, bpo, X, xbs, X, xbs, C, HW, B);
+}
+
 // x += project_out(softmax(normalize(q) normalize(k)^T temperature) v) (:126-139): qkv [B][3C][HW] with a batch stride of qbs, the Gram
-// partials into `part`, the per-image folded matrix into `mt`, then v through it as a per-image 1x1 conv onto X in place
-hipError_t attention(hipStream_t s, const float* qkv, long long qbs, const float* temp, const float* wpo_t, const float* bpo, double* part, float* mt,
-                     float* X, long long xbs, int C, int heads, long long HW, int B)
+// partials into `part`, the per-image folded matrix into `mt`, then v through it as a per-image 1x1 conv onto X in place.  Past 64
+// channels per head the wide kernels do it (`attn` is their scratch, unused below that)
+hipError_t attention(hipStream_t s, const float* qkv, long long qbs, const float* temp, const float* wpo_t, const float* bpo, double* part,
+                     float* attn, float* mt, float* X, long long xbs, int C, int heads, long long HW, int B)
 {
     const int nsplit = nsplit_of(HW, GRAM_CHUNK), ch = C / heads;
+    if (ch > AT_MAXCH) return attention_wide(s, qkv, qbs, temp, wpo_t, bpo, part, attn, mt, X, xbs, C, heads, HW, B);
     hipError_t e;
     GramP p{qkv, qbs, C, ch, HW, GRAM_CHUNK, nsplit, part};
     hipLaunchKernelGGL(rst_gram_kernel, dim3((unsigned)nsplit, (unsigned)heads, (unsigned)B), dim3(256), 0, s, p);
@@ -525,7 +718,7 @@ hipError_t block(xsd_restormer* r, hipStream_t s, const Blk& k, float* X, long l
     hipError_t e;
     if ((e = pw(s, X, xbs, C, P(r, k.n1w), P(r, k.n1b), ln, r->wt + k.qkv.t, 0, P(r, k.qkv.b), nullptr, 0, r->Ta, 3 * C * HW, 3 * C, HW, B))) return e;
     if ((e = dw(s, r->Ta, 3 * C * HW, P(r, k.qkv_dw), P(r, k.qkv_dwb), r->Tb, 3 * C * HW, 3 * C, 0, H, W, B))) return e;
-    if ((e = attention(s, r->Tb, 3 * C * HW, P(r, k.temp), r->wt + k.po.t, P(r, k.po.b), (double*)r->part, r->mt, X, xbs, C, k.heads, HW, B))) return e;
+    if ((e = attention(s, r->Tb, 3 * C * HW, P(r, k.temp), r->wt + k.po.t, P(r, k.po.b), (double*)r->part, r->attn, r->mt, X, xbs, C, k.heads, HW, B))) return e;
     if ((e = pw(s, X, xbs, C, P(r, k.n2w), P(r, k.n2b), ln, r->wt + k.pin.t, 0, P(r, k.pin.b), nullptr, 0, r->Ta, 2 * k.hid * HW, 2 * k.hid, HW, B))) return e;
     if ((e = dw(s, r->Ta, 2 * k.hid * HW, P(r, k.ffn_dw), P(r, k.ffn_dwb), r->Tb, k.hid * HW, k.hid, 1, H, W, B))) return e;
     return pw(s, r->Tb, k.hid * HW, k.hid, nullptr, nullptr, 0, r->wt + k.pout.t, 0, P(r, k.pout.b), X, xbs, X, xbs, C, HW, B);
@@ -544,21 +737,22 @@ hipError_t blocks(xsd_restormer* r, hipStream_t s, const std::vector<Blk>& v, fl
 long long plan_ws(xsd_restormer* r, int B, int H, int W, bool assign)
 {
     const long long d = r->dim, HW1 = (long long)H * W, HW2 = HW1 / 4, HW3 = HW1 / 16, HW4 = HW1 / 64;
-    long long t = 0, part = 0, mt = 0;
+    long long t = 0, part = 0, mt = 0, attn = 0;
     auto level = [&](const std::vector<Blk>& v, long long HW) {
         for (const Blk& k : v) {
             t = std::max(t, std::max(3ll * k.C, 2ll * k.hid) * HW);
             part = std::max(part, (long long)k.heads * nsplit_of(HW, GRAM_CHUNK) * (k.ch * k.ch + 2 * k.ch));
             mt = std::max(mt, (long long)k.C * k.C);
+            if (k.ch > AT_MAXCH) attn = std::max(attn, (long long)k.C * k.ch);       // the wide path's [heads][ch][ch]
         }
     };
     level(r->enc1, HW1); level(r->dec1, HW1); level(r->refine, HW1);
     level(r->enc2, HW2); level(r->dec2, HW2); level(r->enc3, HW3); level(r->dec3, HW3); level(r->lat, HW4);
-    const long long sizes[10] = {B * 2 * d * HW1, B * 4 * d * HW2, B * 2 * d * HW2, B * 8 * d * HW3, B * 4 * d * HW3, B * 8 * d * HW4,
-                                 B * t, B * t, 2 * B * part, B * mt};      // (the Gram partials are doubles)
-    float** ptrs[10] = {&r->slab1, &r->slab2, &r->dec2b, &r->slab3, &r->dec3b, &r->latb, &r->Ta, &r->Tb, &r->part, &r->mt};
+    const long long sizes[11] = {B * 2 * d * HW1, B * 4 * d * HW2, B * 2 * d * HW2, B * 8 * d * HW3, B * 4 * d * HW3, B * 8 * d * HW4,
+                                 B * t, B * t, 2 * B * part, B * mt, B * attn};      // (the Gram partials are doubles)
+    float** ptrs[11] = {&r->slab1, &r->slab2, &r->dec2b, &r->slab3, &r->dec3b, &r->latb, &r->Ta, &r->Tb, &r->part, &r->mt, &r->attn};
     long long off = 0;
-    for (int i = 0; i < 10; ++i) {
+    for (int i = 0; i < 11; ++i) {
         if (assign) *ptrs[i] = (float*)r->ws + off;
         off += (sizes[i] + 63) / 64 * 64;        // 256-B aligned
     }
@@ -583,10 +777,10 @@ int xsd_restormer_create(const xsd_restormer_config* cfg, xsd_restormer** out)
         if (c.num_blocks[l] < 0 || c.num_blocks[l] > 64) return rfail(XSD_ERR_ARG, "Restormer: num_blocks[%d] must be in [0, 64]", l);
         const int C = c.dim << l;
         if (c.heads[l] < 1 || C % c.heads[l]) return rfail(XSD_ERR_ARG, "Restormer: heads[%d] = %d does not divide the %d channels of level %d", l, c.heads[l], C, l + 1);
-        if (C / c.heads[l] > AT_MAXCH) return rfail(XSD_ERR_ARG, "Restormer: %d channels per head at level %d; the engine takes at most %d", C / c.heads[l], l + 1, AT_MAXCH);
+        if (C / c.heads[l] > WD_MAXCH) return rfail(XSD_ERR_ARG, "Restormer: %d channels per head at level %d; the engine takes at most %d", C / c.heads[l], l + 1, WD_MAXCH);
     }
-    if (2 * c.dim / c.heads[0] > AT_MAXCH || (2 * c.dim) % c.heads[0])
-        return rfail(XSD_ERR_ARG, "Restormer: heads[0] = %d must divide the %d decoder level-1 channels into at most %d per head", c.heads[0], 2 * c.dim, AT_MAXCH);
+    if (2 * c.dim / c.heads[0] > WD_MAXCH || (2 * c.dim) % c.heads[0])
+        return rfail(XSD_ERR_ARG, "Restormer: heads[0] = %d must divide the %d decoder level-1 channels into at most %d per head", c.heads[0], 2 * c.dim, WD_MAXCH);
     if (c.num_refinement_blocks < 0 || c.num_refinement_blocks > 64) return rfail(XSD_ERR_ARG, "Restormer: num_refinement_blocks must be in [0, 64]");
     if (!(c.ffn_expansion_factor > 0) || hidden_of(c, c.dim) < 1 || (double)c.dim * 8 * c.ffn_expansion_factor > 65536)
         return rfail(XSD_ERR_ARG, "Restormer: ffn_expansion_factor %g gives no usable hidden width", c.ffn_expansion_factor);
@@ -761,27 +955,46 @@ int xsd_restormer_test_dw(const float* dev_x, const float* dev_w, const float* d
     return XSD_OK;
 }
 
-int xsd_restormer_test_attention(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x, int B,
-                                 int C, int heads, int64_t HW, void* stream)
+namespace {
+
+// both attention hooks: `wide` runs the wide kernels at any width they take, else attention() as the forward calls it, held to the
+// narrow kernels' width
+int test_attention(const char* what, bool wide, const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo,
+                   float* dev_x, int B, int C, int heads, int64_t HW, void* stream)
 {
     if (!dev_qkv || !dev_temperature || !dev_wpo || !dev_x) return rfail(XSD_ERR_ARG, "null argument");
-    if (int rc = check_grid("Restormer attention test", B, HW)) return rc;
-    if (heads < 1 || heads > 65535 || C < 1 || C % heads) return rfail(XSD_ERR_ARG, "Restormer attention test: %d heads do not divide %d channels", heads, C);
-    if (C / heads > AT_MAXCH)
-        return rfail(XSD_ERR_ARG, "Restormer attention test: %d channels per head; the kernels take at most %d", C / heads, AT_MAXCH);
-    if (C > 8192) return rfail(XSD_ERR_ARG, "Restormer attention test: %d channels are outside [1, 8192]", C);
+    if (int rc = check_grid(what, B, HW)) return rc;
+    if (heads < 1 || heads > 65535 || C < 1 || C % heads) return rfail(XSD_ERR_ARG, "%s: %d heads do not divide %d channels", what, heads, C);
+    if (C / heads > (wide ? WD_MAXCH : AT_MAXCH))
+        return rfail(XSD_ERR_ARG, "%s: %d channels per head; the %skernels take at most %d", what, C / heads, wide ? "wide " : "", wide ? WD_MAXCH : AT_MAXCH);
+    if (C > 8192) return rfail(XSD_ERR_ARG, "%s: %d channels are outside [1, 8192]", what, C);
     hipStream_t s = (hipStream_t)stream;
     const int ch = C / heads;
     Scratch sc;
     float* wt = (float*)sc.get(sizeof(float) * (size_t)C * C);
     float* mt = (float*)sc.get(sizeof(float) * (size_t)B * C * C);
+    float* attn = wide ? (float*)sc.get(sizeof(float) * (size_t)B * C * ch) : nullptr;
     double* part = (double*)sc.get(sizeof(double) * (size_t)B * heads * nsplit_of(HW, GRAM_CHUNK) * (ch * ch + 2 * ch));
-    if (!wt || !mt || !part) return rfail(XSD_ERR_NOMEM, "Restormer attention test: allocation failed");
+    if (!wt || !mt || !part || (wide && !attn)) return rfail(XSD_ERR_NOMEM, "%s: allocation failed", what);
     hipError_t e = transpose(s, dev_wpo, wt, C, C);
-    if (!e) e = attention(s, dev_qkv, 3 * C * HW, dev_temperature, wt, dev_bpo, part, mt, dev_x, C * HW, C, heads, HW, B);
+    if (!e) e = (wide ? attention_wide : attention)(s, dev_qkv, 3 * C * HW, dev_temperature, wt, dev_bpo, part, attn, mt, dev_x, C * HW, C, heads, HW, B);
     hipStreamSynchronize(s);
-    if (e) return rfail(XSD_ERR_HIP, "Restormer attention test: %s", hipGetErrorString(e));
+    if (e) return rfail(XSD_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return XSD_OK;
+}
+
+} // namespace
+
+int xsd_restormer_test_attention(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x, int B,
+                                 int C, int heads, int64_t HW, void* stream)
+{
+    return test_attention("Restormer attention test", false, dev_qkv, dev_temperature, dev_wpo, dev_bpo, dev_x, B, C, heads, HW, stream);
+}
+
+int xsd_restormer_test_attention_wide(const float* dev_qkv, const float* dev_temperature, const float* dev_wpo, const float* dev_bpo, float* dev_x,
+                                      int B, int C, int heads, int64_t HW, void* stream)
+{
+    return test_attention("Restormer wide attention test", true, dev_qkv, dev_temperature, dev_wpo, dev_bpo, dev_x, B, C, heads, HW, stream);
 }
 
 int xsd_restormer_test_conv3(const float* dev_x, const float* dev_w, const float* dev_bias, const float* dev_skip, float* dev_y, int B, int cin,

@@ -162,6 +162,7 @@ def load():
     L.xsd_restormer_test_pw.argtypes = [fp, i64, fp, i32, fp, i32, fp, fp, i32, fp, i64, i32, i32, i32, i64, vp]
     L.xsd_restormer_test_dw.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, vp]
     L.xsd_restormer_test_attention.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i64, vp]
+    L.xsd_restormer_test_attention_wide.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i64, vp]
     L.xsd_restormer_test_conv3.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
@@ -181,7 +182,7 @@ ABI_SYMBOLS = [
     "xsd_sw_test_attention", "xsd_sw_test_layernorm", "xsd_hat_test_ca_combine",
     "xsd_swinir_create", "xsd_swinir_destroy", "xsd_swinir_param_count", "xsd_swinir_pack_weights", "xsd_swinir_forward",
     "xsd_swinir_out_size", "xsd_swinir_set_math", "xsd_swinir_get_math", "xsd_swinir_test_pad", "xsd_swinir_test_nearest_conv",
-    "xsd_restormer_test_pw", "xsd_restormer_test_dw", "xsd_restormer_test_attention", "xsd_restormer_test_conv3",
+    "xsd_restormer_test_pw", "xsd_restormer_test_dw", "xsd_restormer_test_attention", "xsd_restormer_test_attention_wide", "xsd_restormer_test_conv3",
 ]
 
 

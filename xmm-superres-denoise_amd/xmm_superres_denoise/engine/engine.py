@@ -674,12 +674,7 @@ def restormer_dw(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = N
     return out
 
 
-@_on_tensor_device
-def restormer_channel_attention(qkv: torch.Tensor, temperature: torch.Tensor, w_po: torch.Tensor, b_po: torch.Tensor | None,
-                                x: torch.Tensor, heads: int) -> torch.Tensor:
-    """Restormer's channel attention behind the depthwise conv, on its own (include/xsd.h: xsd_restormer_test_attention): qkv
-    [B, 3 C, HW], temperature [heads], w_po [C, C] (project_out as stored), b_po [C] or None; x [B, C, HW] is updated IN PLACE,
-    x += project_out(softmax(normalize(q) normalize(k)^T temperature) v), and returned."""
+def _restormer_attention(entry, qkv, temperature, w_po, b_po, x, heads):
     for n, v in (("qkv", qkv), ("temperature", temperature), ("w_po", w_po), ("x", x)):
         _require_cuda_f32(v, n)
     if x.dim() != 3 or tuple(qkv.shape) != (x.shape[0], 3 * x.shape[1], x.shape[2]) or w_po.numel() != x.shape[1] ** 2 or \
@@ -691,9 +686,26 @@ def restormer_channel_attention(qkv: torch.Tensor, temperature: torch.Tensor, w_
         _require_cuda_f32(b_po, "b_po")
         if b_po.numel() != C:
             raise XsdError(f"b_po has {b_po.numel()} elements, not {C}")
-    check(_lib.load().xsd_restormer_test_attention(qkv.data_ptr(), temperature.data_ptr(), w_po.data_ptr(), _ptr(b_po), x.data_ptr(), B, C,
-                                                   int(heads), HW, _stream_ptr(x.device)))
+    check(getattr(_lib.load(), entry)(qkv.data_ptr(), temperature.data_ptr(), w_po.data_ptr(), _ptr(b_po), x.data_ptr(), B, C, int(heads), HW,
+                                      _stream_ptr(x.device)))
     return x
+
+
+@_on_tensor_device
+def restormer_channel_attention(qkv: torch.Tensor, temperature: torch.Tensor, w_po: torch.Tensor, b_po: torch.Tensor | None,
+                                x: torch.Tensor, heads: int) -> torch.Tensor:
+    """Restormer's channel attention behind the depthwise conv, on its own (include/xsd.h: xsd_restormer_test_attention): qkv
+    [B, 3 C, HW], temperature [heads], w_po [C, C] (project_out as stored), b_po [C] or None; x [B, C, HW] is updated IN PLACE,
+    x += project_out(softmax(normalize(q) normalize(k)^T temperature) v), and returned.  At most 64 channels per head."""
+    return _restormer_attention("xsd_restormer_test_attention", qkv, temperature, w_po, b_po, x, heads)
+
+
+@_on_tensor_device
+def restormer_channel_attention_wide(qkv: torch.Tensor, temperature: torch.Tensor, w_po: torch.Tensor, b_po: torch.Tensor | None,
+                                     x: torch.Tensor, heads: int) -> torch.Tensor:
+    """The same through the wide kernels (include/xsd.h: xsd_restormer_test_attention_wide), which the forward runs from 65 to 128
+    channels per head: here at any width up to 128, bitwise equal to restormer_channel_attention where both run."""
+    return _restormer_attention("xsd_restormer_test_attention_wide", qkv, temperature, w_po, b_po, x, heads)
 
 
 RST_CONV3 = {None: 0, "unshuffle": 1, "shuffle": 2}

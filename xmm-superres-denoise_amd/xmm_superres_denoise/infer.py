@@ -128,18 +128,28 @@ def wcs_header(in_header, source_file_name: str, res_mult: int, exposure) -> "Or
     return h
 
 
-def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, device="cuda:0", math: str | None = None):
+def check_dim(name: str, dim: int | None):
+    """`dim` is Restormer's width (models.toml: 24; the published network: 48): with any other model it is refused by name"""
+    if dim is not None and name != "restormer":
+        raise ValueError(f"{name}: dim={dim!r} is not supported: dim is the width of 'restormer' only")
+
+
+def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, device="cuda:0", math: str | None = None,
+               dim: int | None = None):
     """`Model` of the named factory entry (config.MODELS_TOML: rrdb_denoise, esr_gen, swinfir, hat, restormer) with the weights of a checkpoint in
     the reference's key names, with or without Lightning's `model.` prefix (train.load_checkpoint), on `device`.  `math` sets the math
     mode of the network's module (set_math: the RRDB generators take fp32, bf16x6 and f16x3; swinfir and hat fp32 and bf16x6; restormer
-    computes in fp32 only and refuses anything else); None leaves the module's default."""
+    computes in fp32 only and refuses anything else); None leaves the module's default.  `dim` overrides the width of models.toml's restormer
+    entry (24), as the model section of the reference's run config does: dim=48 builds the published Restormer; refused with any other
+    model."""
+    check_dim(name, dim)
     from xmm_superres_denoise.config.config import model_cfg
     from xmm_superres_denoise.models import Model
     from xmm_superres_denoise.train import load_checkpoint
     if name == "restormer" and math not in (None, "fp32"):
         raise ValueError(f"restormer: math mode {math!r} is not supported: the Restormer engine computes in 'fp32' only")
     hr_res = lr_res * (2 if name in ("esr_gen", "swinfir", "hat") else 1)      # SwinFIR, HAT: upscale 2, the class default the factory keeps
-    model = Model(model_cfg(name), (lr_res, lr_res), (hr_res, hr_res))
+    model = Model(model_cfg(name) if dim is None else model_cfg(name, dim=int(dim)), (lr_res, lr_res), (hr_res, hr_res))
     if name == "hat":
         model.configure_model(forward_only_hat=True)      # forward only; a bare configure_model refuses HAT (models/model.py)
     load_checkpoint(checkpoint, model)

@@ -15,7 +15,7 @@ from xmm_superres_denoise.engine import RestormerEngine, XsdError
 
 from .flat_params import FlatParams
 
-MAX_CHANNELS_PER_HEAD = 64      # csrc/restormer.hip: AT_MAXCH
+MAX_CHANNELS_PER_HEAD = 128     # csrc/restormer.hip: WD_MAXCH (past 64 per head the wide channel-attention kernels run)
 
 
 class _LayerNormBody(nn.Module):

@@ -299,7 +299,7 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
          dataset_type: str = "sim", lr_res: int = 416, lr_exps=(20,), hr_exp: int = 100, lr_det_mask=None, hr_det_mask=None,
          agn: int = 1, lr_bkg: int = 1, comb_hr: bool = False, scaling: str = "linear", batch_size: int = 4, loss: str = "l1",
          seed: int | None = None, splits: str | None = None, device: str | None = None, max_pool_bytes: int | None = None,
-         log: bool = True, extended_metrics: bool = False, math: str | None = None, fsim: bool = False) -> dict:
+         log: bool = True, extended_metrics: bool = False, math: str | None = None, fsim: bool = False, dim: int | None = None) -> dict:
     """The reference's `train.py test` (train.py:91-103,165-171) on one device: the test split of the dataset through the model
     of `checkpoint` (any model infer.load_model loads), returning the `test/...` values (loss, get_metrics, get_in_metrics).
     The split file must be the one `fit` wrote (default location: next to the checkpoint); `seed` defaults to the one recorded
@@ -308,9 +308,11 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
     it, get_ext_metrics / get_in_ext_metrics (vif_p, gmsd, ms_gmsd, haarpsi, msdi) are added and the notice names fsim as the one
     metric left out.  `fsim` adds get_fsim_metrics / get_in_fsim_metrics (test/<mode>/fsim, test/<mode>/in/fsim; parity unpinned) for any of
     the five models, with or without `extended_metrics`, and says so (FSIM_ON_NOTICE, or one combined notice when both are given).
-    `math` is infer.load_model's: the math mode of the network (None: its default)."""
+    `math` is infer.load_model's: the math mode of the network (None: its default); so is `dim`, Restormer's width (None: 24 of
+    models.toml), refused with any other model before anything is read."""
     from xmm_superres_denoise.data.datamodule import XmmDataModule
-    from xmm_superres_denoise.infer import load_model
+    from xmm_superres_denoise.infer import check_dim, load_model
+    check_dim(name, dim)
     from xmm_superres_denoise.utils import Loss, create_loss, load_loss_config
     if torch.cuda.device_count() < 1:
         raise RuntimeError("train.py needs an MI355X (no HIP device visible); there is no CPU fallback")
@@ -326,7 +328,7 @@ def test(checkpoint: str, dataset_dir: str, name: str = "rrdb_denoise", dataset_
         with open(splits) as f:
             seed = int(json.load(f).get("seed", 0))
     dm = XmmDataModule(dcfg, splits, seed=seed).setup("test", device=dev, max_pool_bytes=max_pool_bytes)
-    model = load_model(checkpoint, name, lr_res, device=dev, math=math)
+    model = load_model(checkpoint, name, lr_res, device=dev, math=math, dim=dim)
     model.loss = create_loss(*load_loss_config(scaling)) if loss != "l1" else Loss({"l1": 1.0})
     model.metrics, model.in_metrics = _metric_sets(dcfg, "test")
     if extended_metrics:
@@ -353,6 +355,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--math", default=None, choices=[None, "fp32", "bf16x6", "f16x3"])
+    ap.add_argument("--dim", type=int, default=None,
+                    help="test --model restormer: the network's width (default: 24 of models.toml; 48 is the published Restormer)")
     ap.add_argument("--loss", default="l1", choices=["l1", "paper"], help="paper = 0.5 psnr + 0.5 ms_ssim (loss_functions.toml)")
     ap.add_argument("--scaling", default="linear", choices=["linear", "sqrt", "asinh", "log"])
     ap.add_argument("--val-batches", type=int, default=0, help="validation batches after training (loss + metric set)")
@@ -377,13 +381,15 @@ def main():
     a = ap.parse_args()
     if a.routine == "test" and a.model == "restormer" and a.math not in (None, "fp32"):
         ap.error(f"restormer: math mode {a.math!r} is not supported: the Restormer engine computes in 'fp32' only")
+    if a.dim is not None and (a.routine != "test" or a.model != "restormer"):
+        ap.error(f"{a.model}: --dim {a.dim} is not supported: dim is the width of `test --model restormer` only")
     ds = dict(dataset_name=a.dataset_name, dataset_type=a.dataset_type, lr_exps=tuple(a.lr_exps), hr_exp=a.hr_exp,
               lr_det_mask=a.lr_det_mask, hr_det_mask=a.hr_det_mask, agn=a.agn, lr_bkg=a.lr_bkg, comb_hr=a.comb_hr, splits=a.splits)
     if a.routine == "test":
         if not a.checkpoint or not a.dataset_dir:
             ap.error("test needs --checkpoint and --dataset-dir")
         test(a.checkpoint, a.dataset_dir, name=a.model, lr_res=a.lr_res, scaling=a.scaling, batch_size=a.batch_size, loss=a.loss,
-             seed=a.seed, extended_metrics=a.extended_metrics, math=a.math, fsim=a.fsim, **ds)
+             seed=a.seed, extended_metrics=a.extended_metrics, math=a.math, fsim=a.fsim, dim=a.dim, **ds)
     elif a.dataset_dir is None:
         fit(a.model, a.lr_res, a.batch_size, a.steps, checkpoint=a.checkpoint, math=a.math, loss=a.loss, scaling=a.scaling, val_batches=a.val_batches)
     else:
