@@ -516,6 +516,52 @@ int xsd_swinir_test_pad(const float* dev_x, float* dev_y, int B, int C, int H, i
 int xsd_swinir_test_nearest_conv(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int B, int H, int W, int cin, int N,
                                  float slope, int math, void* stream);
 
+/* ---- differentiable Swin ops (csrc/sw_ops.hip) ----------------------------------------------------------------
+ * The four operations of the Swin-family engines (the GEMM as a Linear and as a 3x3 conv, the token LayerNorm, the shifted-window
+ * attention) with one forward and one backward entry each, for torch.autograd.Functions that compose a trainable network in Python
+ * (xmm_superres_denoise/ops.py; models/modules/swinir_train.py).  The forwards of layer_norm and window_attention run the kernels of
+ * xsd_sw_test_layernorm / _attention with the same arguments (the same bits); linear and conv3x3 run a kernel of their own that carries
+ * the whole sum over K and the bias in double and rounds once (within a few ulp of xsd_sw_test_gemm; csrc/sw_ops.hip says why).
+ * Unlike those hooks every entry here is ASYNCHRONOUS on `stream` (no synchronisation) and allocates
+ * nothing: `scratch` is a device buffer of at least the bytes the matching *_scratch query returns (-1 with xsd_last_error for a refused
+ * shape), free to reuse once the call's work on the stream is done.  fp32 only: math 0; 3 ("bf16x6") is refused by name.  Exact fp32
+ * products, sums over K / tokens / pixels in double, no float atomics, every reduction in a fixed order: results are bitwise
+ * reproducible, and da / dx / dqkv of an image do not depend on the batch it shares.  Weights are taken as torch stores them and packed
+ * per call.  act: 0 none, 1 GELU (exact erf), 2 LeakyReLU(slope).
+ *
+ * linear: y [M][N] = act(a [M][K] w[N][K]^T + bias [N] or NULL).  With dev_z (and act != 0) the pre-activation is stored there and
+ * y = act(z) by the epilogue's own expression (the same bits); the backward of an activated op needs it.  backward: dev_dy [M][N] ->
+ * dev_da [M][K], dev_dw [N][K], dev_db [N]; each may be NULL (not computed).  `chunk`: token rows per weight-gradient partial (0: chosen
+ * by the library; the partials are summed in ascending order); the same value goes to the scratch query.  M <= 2^28, K and N <= 65536. */
+int64_t xsd_sw_op_linear_scratch(int64_t M, int K, int N, int act, int64_t chunk, int backward);
+int xsd_sw_op_linear_forward(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, float* dev_z, int64_t M, int K, int N,
+                             int act, float slope, int math, void* scratch, int64_t scratch_bytes, void* stream);
+int xsd_sw_op_linear_backward(const float* dev_dy, const float* dev_a, const float* dev_w, const float* dev_z, float* dev_da, float* dev_dw,
+                              float* dev_db, int64_t M, int K, int N, int act, float slope, int math, int64_t chunk, void* scratch,
+                              int64_t scratch_bytes, void* stream);
+/* conv3x3: x [B][H][W][cin] token-major, w [N][cin][3][3], zero padding 1 -> y [B][H][W][N]; otherwise as linear (dw per tap:
+ * sum over p of x[p + off(tap)][ci] dy[p][co] inside the image; dx: the same conv of dy with the weight flipped and transposed). */
+int64_t xsd_sw_op_conv3x3_scratch(int B, int H, int W, int cin, int N, int act, int64_t chunk, int backward);
+int xsd_sw_op_conv3x3_forward(const float* dev_x, const float* dev_w, const float* dev_bias, float* dev_y, float* dev_z, int B, int H, int W,
+                              int cin, int N, int act, float slope, int math, void* scratch, int64_t scratch_bytes, void* stream);
+int xsd_sw_op_conv3x3_backward(const float* dev_dy, const float* dev_x, const float* dev_w, const float* dev_z, float* dev_dx, float* dev_dw,
+                               float* dev_db, int B, int H, int W, int cin, int N, int act, float slope, int math, int64_t chunk, void* scratch,
+                               int64_t scratch_bytes, void* stream);
+/* layer_norm: as xsd_sw_test_layernorm.  backward: dx [M][C] (or NULL), dw and db [C] (both or neither); the statistics are recomputed
+ * from x in double.  1 <= C <= 4096; the weight gradient takes M <= 65535 * 128 rows. */
+int xsd_sw_op_layernorm_forward(const float* dev_x, const float* dev_w, const float* dev_b, float* dev_y, int64_t M, int C, void* stream);
+int64_t xsd_sw_op_layernorm_scratch(int64_t M, int C);
+int xsd_sw_op_layernorm_backward(const float* dev_dy, const float* dev_x, const float* dev_w, float* dev_dx, float* dev_dw, float* dev_db,
+                                 int64_t M, int C, void* scratch, int64_t scratch_bytes, void* stream);
+/* window_attention: as xsd_sw_test_attention (same limits).  backward: dev_dout [B][H W][C] -> dev_dqkv [B][H W][3 C] (every element
+ * written) and dev_dtable [(2 ws - 1)^2][heads].  The probabilities are recomputed from qkv; the table gradient is one partial per
+ * (window, head) in scratch, summed in a fixed order. */
+int xsd_sw_op_attention_forward(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws,
+                                int shift, float scale, void* stream);
+int64_t xsd_sw_op_attention_scratch(int B, int H, int W, int C, int heads, int ws);
+int xsd_sw_op_attention_backward(const float* dev_dout, const float* dev_qkv, const float* dev_table, float* dev_dqkv, float* dev_dtable, int B,
+                                 int H, int W, int C, int heads, int ws, int shift, float scale, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

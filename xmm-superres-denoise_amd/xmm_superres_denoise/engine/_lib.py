@@ -164,6 +164,20 @@ def load():
     L.xsd_restormer_test_attention.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i64, vp]
     L.xsd_restormer_test_attention_wide.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i64, vp]
     L.xsd_restormer_test_conv3.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
+    for n in ("linear", "conv3x3", "layernorm", "attention"):
+        getattr(L, f"xsd_sw_op_{n}_scratch").restype = i64
+    L.xsd_sw_op_linear_scratch.argtypes = [i64, i32, i32, i32, i64, i32]
+    L.xsd_sw_op_linear_forward.argtypes = [fp, fp, fp, fp, fp, i64, i32, i32, i32, f32, i32, vp, i64, vp]
+    L.xsd_sw_op_linear_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, i64, i32, i32, i32, f32, i32, i64, vp, i64, vp]
+    L.xsd_sw_op_conv3x3_scratch.argtypes = [i32, i32, i32, i32, i32, i32, i64, i32]
+    L.xsd_sw_op_conv3x3_forward.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, f32, i32, vp, i64, vp]
+    L.xsd_sw_op_conv3x3_backward.argtypes = [fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, f32, i32, i64, vp, i64, vp]
+    L.xsd_sw_op_layernorm_forward.argtypes = [fp, fp, fp, fp, i64, i32, vp]
+    L.xsd_sw_op_layernorm_scratch.argtypes = [i64, i32]
+    L.xsd_sw_op_layernorm_backward.argtypes = [fp, fp, fp, fp, fp, fp, i64, i32, vp, i64, vp]
+    L.xsd_sw_op_attention_forward.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
+    L.xsd_sw_op_attention_scratch.argtypes = [i32, i32, i32, i32, i32, i32]
+    L.xsd_sw_op_attention_backward.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp]
     _lib = L
     return L
 
@@ -183,6 +197,9 @@ ABI_SYMBOLS = [
     "xsd_swinir_create", "xsd_swinir_destroy", "xsd_swinir_param_count", "xsd_swinir_pack_weights", "xsd_swinir_forward",
     "xsd_swinir_out_size", "xsd_swinir_set_math", "xsd_swinir_get_math", "xsd_swinir_test_pad", "xsd_swinir_test_nearest_conv",
     "xsd_restormer_test_pw", "xsd_restormer_test_dw", "xsd_restormer_test_attention", "xsd_restormer_test_attention_wide", "xsd_restormer_test_conv3",
+    "xsd_sw_op_linear_scratch", "xsd_sw_op_linear_forward", "xsd_sw_op_linear_backward", "xsd_sw_op_conv3x3_scratch", "xsd_sw_op_conv3x3_forward",
+    "xsd_sw_op_conv3x3_backward", "xsd_sw_op_layernorm_forward", "xsd_sw_op_layernorm_scratch", "xsd_sw_op_layernorm_backward",
+    "xsd_sw_op_attention_forward", "xsd_sw_op_attention_scratch", "xsd_sw_op_attention_backward",
 ]
 
 

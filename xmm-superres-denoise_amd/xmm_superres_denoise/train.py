@@ -158,6 +158,104 @@ def fit(name: str = "rrdb_denoise", lr_res: int = 416, batch_size: int = 4, step
     return model, trainer, losses
 
 
+class SwinIRTrainer:
+    """What fit_swinir trains with, in the shape save_checkpoint / load_checkpoint expect of a trainer (`m`, `v`, `step_count`) and of a
+    model (`model`: the wrapped SwinIR, whose state dict has the reference's key names).  The optimizer is torch.optim.Adam over the
+    SwinIR's own Parameter objects with the reference's rule (lr, betas, eps 1e-8, no weight decay); its moments are views into the
+    two flat buffers `m` and `v` (parameter order), which is what the `adam` block of a checkpoint holds.
+
+    Why torch.optim.Adam and not the engine's xsd_adam_step: that entry belongs to an RRDB engine handle and steps ONE flat buffer
+    with its flat gradient; here autograd delivers one gradient tensor per parameter and the parameters move into a flat buffer only
+    when the fused forward first runs, so the flat form would cost a gather per step for an elementwise update that is a fraction of a
+    percent of the step."""
+
+    def __init__(self, net, lr: float = 2e-4, betas=(0.9, 0.999), loss=None):
+        self.net, self.model, self.loss = net, net.module, loss
+        self.params = [p for p in self.model.parameters() if p.requires_grad]
+        dev = self.params[0].device
+        n = sum(p.numel() for p in self.params)
+        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.opt = torch.optim.Adam(self.params, lr=lr, betas=tuple(betas), eps=1e-8, weight_decay=0.0)
+        off = 0
+        for p in self.params:
+            k = p.numel()
+            self.opt.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.m[off:off + k].view(p.shape),
+                                 "exp_avg_sq": self.v[off:off + k].view(p.shape)}
+            off += k
+
+    @property
+    def step_count(self) -> int:
+        return int(self.opt.state[self.params[0]]["step"].item())
+
+    @step_count.setter
+    def step_count(self, n: int):
+        for p in self.params:
+            self.opt.state[p]["step"].fill_(float(n))
+
+    def train_step(self, lr_img: torch.Tensor, hr_img: torch.Tensor) -> torch.Tensor:
+        self.net.train()
+        self.opt.zero_grad(set_to_none=True)
+        y = self.net(lr_img)
+        if self.loss is None:
+            loss = torch.nn.functional.l1_loss(y, hr_img)
+            loss.backward()
+        else:       # the composed loss is an engine kernel with its own gradient (utils.Loss.value_and_grad)
+            loss, dy = self.loss.value_and_grad(y.detach().contiguous(), hr_img)
+            y.backward(dy)
+        self.opt.step()
+        return loss.detach()
+
+
+def fit_swinir(ctor_kwargs: dict, steps: int = 10, batch_size: int = 1, lr_res: int = 64, data=None, lr: float = 2e-4,
+               betas=(0.9, 0.999), loss="l1", clamp: bool = False, seed: int = 0, checkpoint: str | None = None,
+               device: str | None = None, log_every: int = 1):
+    """Train a SwinIR on the MI355X engine: `SwinIR(**ctor_kwargs)` (the reference's constructor arguments), wrapped in a
+    TrainableSwinIR (models/modules/swinir_train.py: the forward composed of the differentiable HIP ops of xmm_superres_denoise/ops.py),
+    Adam with the reference's rule.  Single device; `fit` is untouched and keeps refusing the transformers by name.
+
+    data: None = random tiles for `steps` steps (the BoringDataset analogue of `fit`: lr [B, in_chans, lr_res, lr_res], hr at the
+    network's output size), or any iterable of (lr, hr) CUDA batches, e.g.
+    `(dm.dataset.batch(idx, 0) for idx in dm.batches("train", batch_size, 0))` of an XmmDataModule (at most `steps` of them; steps=None
+    takes them all).  loss: "l1" (torch's l1_loss on the output: one elementwise pass; the engine's xsd_l1_loss belongs to an RRDB engine
+    handle) or a create_loss(...) object (the engine's loss kernels with their own gradient).  clamp: the [0, 1] clamp of Model.forward on the training output.
+    checkpoint: written in save_checkpoint's layout (reference key names + the `adam` block); infer.load_swinir(checkpoint,
+    **ctor_kwargs) loads it and load_checkpoint(path, trainer, trainer) restores the moments.
+    Returns (trainable net, trainer, losses)."""
+    from xmm_superres_denoise.models import SwinIR, TrainableSwinIR
+    if torch.cuda.device_count() < 1:
+        raise RuntimeError("train.py needs an MI355X (no HIP device visible); there is no CPU fallback")
+    if loss != "l1" and not hasattr(loss, "value_and_grad"):
+        raise ValueError(f"fit_swinir: loss {loss!r} is not supported (\"l1\" or a create_loss(...) object)")
+    dev = torch.device(device or "cuda:0")
+    torch.cuda.set_device(dev)
+    torch.manual_seed(seed)
+    module = SwinIR(**ctor_kwargs).to(dev)
+    net = TrainableSwinIR(module, generator=torch.Generator(device=dev).manual_seed(seed + 2), clamp=clamp)
+    trainer = SwinIRTrainer(net, lr=lr, betas=betas, loss=None if loss == "l1" else loss)
+    if data is None:
+        g = torch.Generator().manual_seed(seed + 1)
+        Ho, Wo = module.out_size(lr_res, lr_res)
+
+        def tiles():
+            while True:
+                yield (torch.rand((batch_size, module.in_chans, lr_res, lr_res), generator=g).to(dev),
+                       torch.rand((batch_size, module.in_chans, Ho, Wo), generator=g).to(dev))
+        data = tiles()
+        steps = 10 if steps is None else steps
+    losses = []
+    for it, (lr_img, hr_img) in enumerate(data):
+        if steps is not None and it >= steps:
+            break
+        losses.append(float(trainer.train_step(lr_img, hr_img)))
+        if log_every and it % log_every == 0:
+            print(f"step {it}: train/loss {losses[-1]:.6f}", flush=True)
+    net.eval()
+    if checkpoint:
+        save_checkpoint(checkpoint, trainer, trainer, epoch=0)
+    return net, trainer, losses
+
+
 def dataset_cfg(dataset_dir, dataset_name="sim_dataset", dataset_type="sim", name="rrdb_denoise", lr_res=416, lr_exps=(20,),
                 hr_exp=100, lr_det_mask=None, hr_det_mask=None, agn=1, lr_bkg=1, comb_hr=False, scaling="sqrt", batch_size=1):
     """the [dataset] section of the reference's run config (res/baseline_config.toml) for `name`: HR at lr_res for the
