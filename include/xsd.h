@@ -603,6 +603,44 @@ int xsd_test_conv3x3_bwd(xsd_engine* e, const float* const* host_in_planes, int 
                          const float* dev_g_plane, float* const* host_dx_planes, float* dev_dw_oihw, float* dev_db,
                          int B, int H, int W, void* stream);
 
+/* One output chunk (32 channels) of xsd_test_conv3x3_ex and its fused epilogue, in the kernels' order:
+ *   v = conv + bias; v *= a1; if (accumulate) v += p; if (e1) v += s1 * e1; v *= a2; if (e2) v += s2 * e2; if (e3) v += s3 * e3;
+ *   v = v > 0 ? v : v * slope; if (mask) v = mask > 0 ? v : v * mslope; p = v
+ * e1, e2, e3, mask: device planes [B][H][W][32] or NULL.  bits_out (split math modes): receives the compact mask of the stored values,
+ * one 16-bit word per pixel and lane half h, [B][H][W][2]: bit 4q + t <-> channel 8q + 4h + t is > 0.  bits_in (with mask): such words,
+ * read instead of the mask plane. */
+typedef struct xsd_test_out {
+    float* p;
+    const float* e1;
+    const float* e2;
+    const float* e3;
+    const float* mask;
+    float a1, s1, a2, s2, s3, slope, mslope;
+    int accumulate;
+    unsigned short* bits_out;
+    const unsigned short* bits_in;
+} xsd_test_out;
+/* One conv launch of the engine's math mode with a caller-supplied epilogue per output chunk (kernel-level tests; synchronous).
+ * Inputs: n_in planes [B][H][W][32] (host array of device pointers), or with shuffle_in != 0 ONE plane [B][2H][2W][32] in host_in_planes[0]
+ * read as its four sub-pixel views (n_in must be 4; view n = 2i + j holds pixels (2y + i, 2x + j)).  Outputs: n_out chunks (n_in > 1 and
+ * n_out > 1 exclude each other, both <= 5), or with shuffle_out != 0 the four sub-pixel views of ONE plane [B][2H][2W][32], outs[0].p
+ * (n_out must be 4; the other fields are still per chunk).  dev_w_oihw: [32 n_out][32 n_in][3][3], chunk j = output channels 32j .. 32j + 31;
+ * dev_bias: [32 n_out] or NULL.  host_amax11 (or NULL): in math mode f16x3 receives the launch's max-|x| slots -- [0..4] the input planes or
+ * views, [5] the packed weights, [6..10] the output chunks (zeroed before the launch) -- and zeros in the other modes.
+ * A launch the kernel's launcher refuses returns XSD_ERR_HIP and writes nothing. */
+int xsd_test_conv3x3_ex(xsd_engine* e, const float* const* host_in_planes, int n_in, int shuffle_in, const float* dev_w_oihw,
+                        const float* dev_bias, const xsd_test_out* host_outs, int n_out, int shuffle_out, float* host_amax11,
+                        int B, int H, int W, void* stream);
+/* One weight-gradient launch over the n_in x n_g rectangle of (X, G) plane pairs plus its fixed-order reduction into dev_dw_oihw
+ * [cout_total][cin_total][3][3] and dev_db [cout_total] (kernel-level tests; synchronous; the number of partial sums follows the plan's rule).
+ * G: n_g planes [B][H][W][32], or with shuffle_g != 0 ONE plane [B][2H][2W][32] in host_g_planes[0] read as its four sub-pixel views
+ * (n_g must be 4).  The launch writes input channels 32 j0 .. 32 (j0 + n_in) - 1 of output channels 32 (n0 + n) + co, or with shuffle != 0
+ * (n_g = 4) of output channels 4 (32 plane + co) + n; everything is multiplied by `scale`.  Refused with XSD_ERR_ARG: n_in > 5, n_g > 4,
+ * a rectangle the partial-sum buffer does not hold, a block outside [cout_total][cin_total]. */
+int xsd_test_wgrad_ex(xsd_engine* e, const float* const* host_x_planes, int n_in, const float* const* host_g_planes, int n_g, int shuffle_g,
+                      float scale, int shuffle, int plane, int j0, int n0, int cin_total, int cout_total,
+                      float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import oracle
-from util_hip import nchw_to_planes, planes_to_nchw, ptr_array
+from util_hip import guarded_planes as _guarded_planes, nchw_to_planes, planes_to_nchw, ptr_array
 
 pytestmark = pytest.mark.gpu
 
@@ -109,27 +109,6 @@ def test_l1_loss_kernel(eng):
     assert abs(loss.item() - np.abs(y.astype(np.float64) - t).mean()) < 1e-6
     ref = np.sign(y - t) / y.size
     assert np.allclose(dy.cpu().numpy(), ref, rtol=1e-6, atol=0)
-
-
-def _guarded_planes(n, B, H, W, fill, guard_px=4096):
-    """n planes [B][H][W][32] carved out of ONE allocation with NaN guard bands in front of, between and behind them; returns
-    (planes, check) where check() asserts that every guard element is still NaN (a stray store of any kernel lands there or on a
-    neighbouring plane, which the value checks catch)."""
-    plane = B * H * W * 32
-    g = guard_px * 32
-    buf = torch.full(((n + 1) * g + n * plane,), float("nan"), device="cuda")
-    planes = []
-    for i in range(n):
-        p = buf[(i + 1) * g + i * plane:(i + 1) * g + (i + 1) * plane].view(B, H, W, 32)
-        if fill is not None:
-            p.copy_(fill[i])
-        planes.append(p)
-
-    def check():
-        for i in range(n + 1):
-            band = buf[i * (g + plane):i * (g + plane) + g]
-            assert bool(torch.isnan(band).all()), f"guard band {i} was written"
-    return planes, check
 
 
 @pytest.mark.parametrize("n_in", [1, 3, 5])

@@ -51,6 +51,27 @@ def ptr_array(tensors):
     return arr
 
 
+def guarded_planes(n, B, H, W, fill, guard_px=4096):
+    """n planes [B][H][W][32] carved out of ONE allocation with NaN guard bands in front of, between and behind them; returns
+    (planes, check) where check() asserts that every guard element is still NaN (a stray store of any kernel lands there or on a
+    neighbouring plane, which the value checks catch)."""
+    plane = B * H * W * 32
+    g = guard_px * 32
+    buf = torch.full(((n + 1) * g + n * plane,), float("nan"), device="cuda")
+    planes = []
+    for i in range(n):
+        p = buf[(i + 1) * g + i * plane:(i + 1) * g + (i + 1) * plane].view(B, H, W, 32)
+        if fill is not None:
+            p.copy_(fill[i])
+        planes.append(p)
+
+    def check():
+        for i in range(n + 1):
+            band = buf[i * (g + plane):i * (g + plane) + g]
+            assert bool(torch.isnan(band).all()), f"guard band {i} was written"
+    return planes, check
+
+
 def flip_candidates(kind, blocks, state, x, t, nup=1, eps=4e-6, return_clamp_mask=False, device="cpu"):
     """Where can two fp32-accurate implementations legitimately take different branches of the network's step functions?
     A float64 evaluation of the reference graph (rrdb_blocks.py:37-54, generator_rrdb.py:66-137) records, for every conv

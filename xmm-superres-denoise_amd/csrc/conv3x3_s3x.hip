@@ -558,8 +558,14 @@ hipError_t launch_conv3x3_s3x(const ConvParams& p, hipStream_t stream)
     }, &ncu);
     if (e != hipSuccess) return e;
     if (p.n_in < 1 || p.n_out < 1 || p.n_in * p.n_out > 5 || !p.zero) return hipErrorInvalidValue;
-    for (int j = 0; j < p.n_out; ++j)       // deferred stores: 32-bit BYTE offsets against a descriptor of H * rs * 4 bytes
-        if ((long long)p.H * p.out[j].rs * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+    for (int j = 0; j < p.n_out; ++j) {
+        const OutDesc& o = p.out[j];
+        // compact masks: only the combinations the epilogue has variants for (any other would run the generic variant, which
+        // writes no mask words at all, and report success)
+        if (o.bits_out && (o.accumulate || o.e1 || o.e2 || o.e3 || o.mask)) return hipErrorInvalidValue;
+        // deferred stores: 32-bit BYTE offsets against a descriptor of H * rs * 4 bytes
+        if ((long long)p.H * o.rs * 4 >= (1ll << 31)) return hipErrorInvalidValue;
+    }
     for (int i = 0; i < p.n_in; ++i)        // the staging waves take every input's lane offsets and range from in[0]'s strides
         if (p.in[i].rs != p.in[0].rs || p.in[i].ps != p.in[0].ps) return hipErrorInvalidValue;
     if ((long long)p.H * p.in[0].rs * 4 >= (1ll << 31)) return hipErrorInvalidValue;

@@ -161,6 +161,23 @@ static hipError_t launch_wgrad_split(int math, int ablate, const WgradParams& p,
     return (math == 4 && !(ablate & (1 << 22))) ? launch_wgrad_h2x(p, s) : launch_wgrad_s3x(p, s);
 }
 
+// Parts (partial sums) of one weight-gradient launch over the n_in x n_g rectangle: the plan (Builder::wgrad_launch) and the single-launch
+// test hook (xsd_test_wgrad_ex) both ask here, so the hook cannot drift from the plan.
+static int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
+{
+#ifndef XSD_WGRAD_ROUNDS
+    // The grid is nparts x n_in x n_g workgroups of one per CU: with nparts = the CU count a launch over k (X, G) pairs runs k
+    // rounds of workgroups, and every round pays a workgroup's fixed cost again (first two tiles' round trips, the final
+    // LDS reduction and partial-sum store, ~30 us of a ~450 us round: kernel trace, 0.476 / 0.911 / 1.359 / 1.731 / 2.250 ms
+    // for 1..5 pairs).  Where the pairs divide the CUs into a multiple of eight parts (2 and 4 pairs: 128 / 64 parts) the whole
+    // launch is ONE round of k-times longer workgroups; the workgroups that share G tiles still run side by side on one XCD.
+    // 3 and 5 pairs would leave 16 CUs idle (240 workgroups): they keep the k rounds.
+    const int pairs = n_in * n_g;
+    if (e->math >= 3 && pairs > 1 && e->nparts % pairs == 0 && ((e->nparts / pairs) & 7) == 0) return e->nparts / pairs;   // (the split modes' kernels: one workgroup per CU; the exact-fp32 kernel runs two)
+#endif
+    return e->nparts;
+}
+
 // Profile classes of xsd_profile_read (include/xsd.h): 0 conv (forward + input-gradient), 1 weight gradient; the HBM-bound kernels:
 // 2 edge_expand (1 -> 32), 3 edge_reduce (32 -> 1), 4 edge_wgrad, 5 L1 loss, 6 Adam, 7 clamp backward, 8 plane max |x| sweeps.
 // `bytes` is ALGORITHMIC traffic (SURVEY 8d rule: every operand once), `flop` 2 x MAC.
@@ -418,19 +435,7 @@ struct Builder {
     {
         xsd_engine* eng = e;
         WgradParams wp = wgrad_base(level);
-        wp.n_in = (int)xs.size(); wp.n_g = (int)gs.size(); wp.nparts = e->nparts;
-#ifndef XSD_WGRAD_ROUNDS
-        // The grid is nparts x n_in x n_g workgroups of one per CU: with nparts = the CU count a launch over k (X, G) pairs runs k
-        // rounds of workgroups, and every round pays a workgroup's fixed cost again (first two tiles' round trips, the final
-        // LDS reduction and partial-sum store, ~30 us of a ~450 us round: kernel trace, 0.476 / 0.911 / 1.359 / 1.731 / 2.250 ms
-        // for 1..5 pairs).  Where the pairs divide the CUs into a multiple of eight parts (2 and 4 pairs: 128 / 64 parts) the whole
-        // launch is ONE round of k-times longer workgroups; the workgroups that share G tiles still run side by side on one XCD.
-        // 3 and 5 pairs would leave 16 CUs idle (240 workgroups): they keep the k rounds.
-        {
-            const int pairs = wp.n_in * wp.n_g;
-            if (e->math >= 3 && pairs > 1 && e->nparts % pairs == 0 && ((e->nparts / pairs) & 7) == 0) wp.nparts = e->nparts / pairs;   // (the split modes' kernels: one workgroup per CU; the exact-fp32 kernel runs two)
-        }
-#endif
+        wp.n_in = (int)xs.size(); wp.n_g = (int)gs.size(); wp.nparts = wgrad_nparts(e, wp.n_in, wp.n_g);
         for (size_t i = 0; i < xs.size(); ++i) wp.x[i] = xs[i];
         for (size_t i = 0; i < gs.size(); ++i) wp.g[i] = gs[i];
         std::vector<Launch> pre;     // math mode 4: reductions for planes nobody has reported yet
@@ -1565,6 +1570,97 @@ int xsd_test_conv3x3_bwd(xsd_engine* e, const float* const* in_planes, int n_in,
     hipStreamSynchronize(s);
     hipFree(fwd); hipFree(bwd);
     if (err != hipSuccess) return fail(XSD_ERR_HIP, "bwd launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+// One conv launch with a caller-supplied epilogue per output chunk and, optionally, pixel-shuffled views on either side
+// (include/xsd.h).  Planes and views come from the Builder's own std_in / shuf_in / std_out / shuf_out, the launch goes
+// through run_conv: what is tested is the engine's code.
+int xsd_test_conv3x3_ex(xsd_engine* e, const float* const* in_planes, int n_in, int shuffle_in, const float* dev_w_oihw, const float* dev_bias,
+                        const xsd_test_out* outs, int n_out, int shuffle_out, float* host_amax11, int B, int H, int W, void* stream)
+{
+    if (!e || !in_planes || !outs || !dev_w_oihw || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
+    if (n_in < 1 || n_in > 5 || n_out < 1 || n_out > 5 || (n_in > 1 && n_out > 1)) return fail(XSD_ERR_ARG, "bad n_in/n_out");
+    if ((shuffle_in && n_in != 4) || (shuffle_out && n_out != 4)) return fail(XSD_ERR_ARG, "a pixel-shuffled side has exactly four views");
+    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
+    for (int i = 0; i < (shuffle_in ? 1 : n_in); ++i) if (!in_planes[i]) return fail(XSD_ERR_ARG, "null input plane");
+    for (int j = 0; j < (shuffle_out ? 1 : n_out); ++j) if (!outs[j].p) return fail(XSD_ERR_ARG, "null output plane");
+    hipStream_t s = (hipStream_t)stream;
+    float *fwd = nullptr, *bwd = nullptr;
+    int rc = pack_single(dev_w_oihw, 32 * n_out, 32 * n_in, &fwd, &bwd, e->math, s, e->amax + e->amax_cap - 4);
+    if (rc) return rc;
+    Builder b(e, B, H, W, false, 0);
+    ConvParams p = b.conv_base(0);
+    p.n_in = n_in; p.n_out = n_out; p.wpanel = fwd; p.bias = dev_bias;
+    p.amax_w = e->amax + e->amax_cap - 4;     // mode 4: max |w| of the forward panels (pack_single)
+    for (int i = 0; i < n_in; ++i) p.in[i] = shuffle_in ? b.shuf_in(in_planes[0], 0, i) : b.std_in(in_planes[i], 0);
+    float* oslot = e->amax + e->amax_cap - 24;    // mode 4: one slot per output chunk (CAP-32.. are run_conv's input slots)
+    for (int j = 0; j < n_out; ++j) {
+        const xsd_test_out& t = outs[j];
+        OutDesc& o = p.out[j];
+        if (shuffle_out) b.shuf_out(o, outs[0].p, 0, j); else b.std_out(o, t.p, 0);
+        o.e1 = t.e1; o.e2 = t.e2; o.e3 = t.e3; o.mask = t.mask;
+        o.a1 = t.a1; o.s1 = t.s1; o.a2 = t.a2; o.s2 = t.s2; o.s3 = t.s3; o.slope = t.slope; o.mslope = t.mslope;
+        o.accumulate = t.accumulate; o.bits_out = t.bits_out; o.bits_in = t.bits_in;
+        if (e->math == 4) o.amax = oslot + j;
+    }
+    hipError_t err = e->math == 4 ? hipMemsetAsync(oslot, 0, 5 * sizeof(float), s) : hipSuccess;
+    if (err == hipSuccess) err = run_conv(e, p, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err == hipSuccess && host_amax11) {
+        for (int k = 0; k < 11; ++k) host_amax11[k] = 0.f;
+        if (e->math == 4) {
+            err = hipMemcpy(host_amax11, e->amax + e->amax_cap - 32, n_in * sizeof(float), hipMemcpyDeviceToHost);
+            if (err == hipSuccess) err = hipMemcpy(host_amax11 + 5, p.amax_w, sizeof(float), hipMemcpyDeviceToHost);
+            if (err == hipSuccess) err = hipMemcpy(host_amax11 + 6, oslot, n_out * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    hipFree(fwd); hipFree(bwd);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "conv launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+// One weight-gradient launch over the n_in x n_g rectangle plus its fixed-order reduction, with the reduction's fields from the caller.
+int xsd_test_wgrad_ex(xsd_engine* e, const float* const* x_planes, int n_in, const float* const* g_planes, int n_g, int shuffle_g,
+                      float scale, int shuffle, int plane, int j0, int n0, int cin_total, int cout_total,
+                      float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream)
+{
+    if (!e || !x_planes || !g_planes || !dev_dw_oihw || !dev_db || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
+    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
+    if (n_in < 1 || n_in > 5 || n_g < 1 || n_g > 4) return fail(XSD_ERR_ARG, "bad n_in/n_g (at most 5 X and 4 G planes)");
+    if (shuffle_g && n_g != 4) return fail(XSD_ERR_ARG, "a pixel-shuffled G plane has exactly four views");
+    if (shuffle && n_g != 4) return fail(XSD_ERR_ARG, "the shuffled reduction takes the four sub-pixel gradients (n_g = 4)");
+    const int nparts = wgrad_nparts(e, n_in, n_g);
+    // wg_partial holds nparts x 5 panels, wg_bias_partial nparts x 4 x 32 sums (xsd_create)
+    if ((long long)nparts * n_in * n_g > (long long)e->nparts * 5) return fail(XSD_ERR_ARG, "%d x %d pairs over %d parts do not fit the partial-sum buffer", n_in, n_g, nparts);
+    if (j0 < 0 || n0 < 0 || plane < 0 || cin_total < 32 * (j0 + n_in)) return fail(XSD_ERR_ARG, "the launch's input planes lie outside cin_total");
+    if (shuffle ? cout_total < 128 * (plane + 1) : cout_total < 32 * (n0 + n_g)) return fail(XSD_ERR_ARG, "the launch's output chunks lie outside cout_total");
+    for (int i = 0; i < n_in; ++i) if (!x_planes[i]) return fail(XSD_ERR_ARG, "null X plane");
+    for (int i = 0; i < (shuffle_g ? 1 : n_g); ++i) if (!g_planes[i]) return fail(XSD_ERR_ARG, "null G plane");
+    hipStream_t s = (hipStream_t)stream;
+    Builder b(e, B, H, W, false, 0);
+    WgradParams wp = b.wgrad_base(0);
+    wp.n_in = n_in; wp.n_g = n_g; wp.nparts = nparts;
+    for (int i = 0; i < n_in; ++i) wp.x[i] = b.std_in(x_planes[i], 0);
+    for (int i = 0; i < n_g; ++i) wp.g[i] = shuffle_g ? b.shuf_in(g_planes[0], 0, i) : b.std_in(g_planes[i], 0);
+    wp.partial = e->wg_partial; wp.bias_partial = e->wg_bias_partial; wp.zero = e->zero_page; wp.ablate = e->ablate;
+    hipError_t err = hipSuccess;
+    if (e->math == 4) {   // nobody has reported the operands' max |x|: reduce them here (the weight-gradient hooks' slots, CAP-16 .. CAP-5)
+        float* t = e->amax + e->amax_cap - 16;
+        err = hipMemsetAsync(t, 0, 12 * sizeof(float), s);
+        for (int i = 0; i < n_in && err == hipSuccess; ++i) { err = launch_plane_amax(wp.x[i], B, H, W, t + i, s); wp.amax_x[i] = t + i; }
+        for (int i = 0; i < n_g && err == hipSuccess; ++i) { err = launch_plane_amax(wp.g[i], B, H, W, t + 5 + i, s); wp.amax_g[i] = t + 5 + i; }
+    }
+    if (err == hipSuccess) err = e->math >= 3 ? launch_wgrad_split(e->math, e->ablate, wp, s) : launch_wgrad_mfma(wp, s);
+    if (err == hipSuccess) {
+        WgradReduceParams rp; memset(&rp, 0, sizeof(rp));
+        rp.partial = e->wg_partial; rp.bias_partial = e->wg_bias_partial; rp.nparts = wp.nparts; rp.n_in = n_in; rp.n_g = n_g;
+        rp.cin_total = cin_total; rp.cout_total = cout_total; rp.shuffle = shuffle; rp.scale = scale; rp.j0 = j0; rp.n0 = n0; rp.plane = plane;
+        rp.dw = dev_dw_oihw; rp.db = dev_db;
+        err = launch_wgrad_reduce(rp, s);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient launch: %s", hipGetErrorString(err));
     return XSD_OK;
 }
 

@@ -22,6 +22,13 @@ class XsdConfig(ctypes.Structure):
                  "memory_efficient", "reserved")]
 
 
+class XsdTestOut(ctypes.Structure):      # xsd_test_out (include/xsd.h): one output chunk of xsd_test_conv3x3_ex and its fused epilogue
+    _fields_ = [("p", ctypes.c_void_p), ("e1", ctypes.c_void_p), ("e2", ctypes.c_void_p), ("e3", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("a1", ctypes.c_float), ("s1", ctypes.c_float), ("a2", ctypes.c_float), ("s2", ctypes.c_float), ("s3", ctypes.c_float),
+                ("slope", ctypes.c_float), ("mslope", ctypes.c_float), ("accumulate", ctypes.c_int32),
+                ("bits_out", ctypes.c_void_p), ("bits_in", ctypes.c_void_p)]
+
+
 class XsdRestormerConfig(ctypes.Structure):
     _fields_ = [("inp_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("dim", ctypes.c_int32),
                 ("num_blocks", ctypes.c_int32 * 4), ("num_refinement_blocks", ctypes.c_int32), ("heads", ctypes.c_int32 * 4),
@@ -114,6 +121,8 @@ def load():
     L.xsd_probe_mfma_stream.argtypes = [i32, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), vp]
     L.xsd_test_conv3x3.argtypes = [vp, ctypes.POINTER(vp), i32, fp, fp, ctypes.POINTER(vp), i32, f32, i32, i32, i32, vp]
     L.xsd_test_conv3x3_bwd.argtypes = [vp, ctypes.POINTER(vp), i32, fp, fp, ctypes.POINTER(vp), fp, fp, i32, i32, i32, vp]
+    L.xsd_test_conv3x3_ex.argtypes = [vp, ctypes.POINTER(vp), i32, i32, fp, fp, ctypes.POINTER(XsdTestOut), i32, i32, ctypes.POINTER(f32), i32, i32, i32, vp]
+    L.xsd_test_wgrad_ex.argtypes = [vp, ctypes.POINTER(vp), i32, ctypes.POINTER(vp), i32, i32, f32, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, vp]
     L.xsd_restormer_create.argtypes = [ctypes.POINTER(XsdRestormerConfig), ctypes.POINTER(vp)]
     L.xsd_restormer_destroy.argtypes = [vp]
     L.xsd_restormer_destroy.restype = None
@@ -187,7 +196,7 @@ ABI_SYMBOLS = [
     "xsd_last_error", "xsd_version", "xsd_create", "xsd_destroy", "xsd_param_count", "xsd_set_math", "xsd_get_math", "xsd_pack_weights",
     "xsd_forward", "xsd_backward", "xsd_backward_num_stages", "xsd_backward_stage", "xsd_grad_range",
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_ext_metrics_create", "xsd_ext_metrics_destroy", "xsd_ext_metrics_eval", "xsd_fsim_create", "xsd_fsim_destroy", "xsd_fsim_eval", "xsd_fsim_test_dft2", "xsd_fsim_test_median", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_compose_batch", "xsd_normalize", "xsd_image_upsample",
-    "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd",
+    "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd", "xsd_test_conv3x3_ex", "xsd_test_wgrad_ex",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
