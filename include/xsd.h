@@ -641,6 +641,62 @@ int xsd_test_wgrad_ex(xsd_engine* e, const float* const* host_x_planes, int n_in
                       float scale, int shuffle, int plane, int j0, int n0, int cin_total, int cout_total,
                       float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream);
 
+/* The edge layers one by one (csrc/aux_kernels.hip; kernel-level tests; synchronous; an engine of the plane path).  Every hook packs
+ * ONE (32, 9) weight block with the engine's own packer (pack_edge_kernel) and launches through the engine's own launcher.
+ * dev_w with w_last == 0: W_first[:, ch], 32 rows of 9 taps `first_cstride` (= 9 * in_channels) floats apart; with w_last != 0:
+ * W_last[o], [32][9].  flipped != 0 selects the packed form with the taps reversed (the input-gradient forms).
+ * A launch the launcher refuses returns XSD_ERR_HIP and writes nothing. */
+/* 1 -> 32: out[B][H][W][32] (+)= bias + sum_tap s[p + tap] w[tap][c]; then the mask select (mask plane, or its compact words `bits`
+ * in the layout of xsd_test_out.bits_out): kept where the mask is > 0, times mslope elsewhere.  s_bs: floats between images of s
+ * (0: H * W).  dev_amax (or NULL): slot that receives max |out| by an atomic maximum (the caller zeroes it). */
+int xsd_test_edge_expand(xsd_engine* e, const float* dev_s, long long s_bs, const float* dev_w, int w_last, int flipped, int first_cstride,
+                         const float* dev_bias, float* dev_out, const float* dev_mask, float mslope, const unsigned short* dev_bits,
+                         int accumulate, float* dev_amax, int B, int H, int W, void* stream);
+/* 32 -> 1: v = bias + sum_tap sum_c f[p + tap][c] w[tap][c] (+ skip) (+ addto); pre = v; y = clamp01 ? clamp(v, 0, 1) : v.
+ * y_bs: floats between images of y / pre / addto, skip_bs: of skip (0: H * W). */
+int xsd_test_edge_reduce(xsd_engine* e, const float* dev_f, const float* dev_w, int w_last, int flipped, int first_cstride,
+                         const float* dev_bias, const float* dev_skip, long long skip_bs, float* dev_pre, float* dev_y, long long y_bs,
+                         int clamp01, const float* dev_addto, int B, int H, int W, void* stream);
+/* Edge weight gradient of f [B][H][W][32] against s [B][H][W] (s_bs as above) plus its fixed-order final sum.  mode 0 (conv_first):
+ * dw[c * cstride + tap], db[c] = sum f; mode 1 (conv_last): dw[c * 9 + 8 - tap], db[0] = sum s.  nblocks 0: the engine's own rule
+ * (the function the plan asks), else that many workgroups (at most the rule's: the partial-sum buffer); *host_nblocks = what ran. */
+int xsd_test_edge_wgrad(xsd_engine* e, const float* dev_f, const float* dev_s, long long s_bs, int mode, float* dev_dw, float* dev_db,
+                        int cstride, int nblocks, int* host_nblocks, int B, int H, int W, void* stream);
+
+/* The generic-width kernels one by one (csrc/generic_net.hip; kernel-level tests; synchronous; no engine: each call builds a GenericNet
+ * that is ONE conv (cout, cin), packs it with the net's own pack() and calls the net's own conv() / wgrad(), dispatch included).
+ * Tensors are NCHW views: channel stride H * W, batch stride given.  The epilogue in the kernels' order:
+ *   v = (conv + bias) * a1; if (e1 && ch < e1c) v += s1 * e1; v *= a2; if (e2) v += s2 * e2; v = v > 0 ? v : v * slope;
+ *   if (skip) v += skip[skipc == 1 ? 0 : ch]; if (accumulate) v += y; if (pre) pre = v; if (clamp01) v = clamp(v, 0, 1); y = v
+ * shuffle: y (and pre) are [B][cout / 4][2H][2W], channel oc -> (oc >> 2, sub-pixel ((oc >> 1) & 1, oc & 1)). */
+typedef struct xsd_test_gconv_args {
+    const float* x; long long xbs;
+    float* y; long long ybs;
+    float a1; const float* e1; long long e1bs; float s1; int e1c;
+    float a2; const float* e2; long long e2bs; float s2;
+    float slope; int accumulate; int shuffle;
+    const float* skip; long long skipbs; int skipc;
+    float* pre; int clamp01;
+} xsd_test_gconv_args;
+/* dev_params: the flat parameter buffer; the conv's OIHW weight stands at param_off, its bias behind it.  transposed != 0: the
+ * input-gradient conv (cout -> cin channels, flipped taps, no bias).  *host_path: 1 = direct kernel, 2 = matrix-instruction kernel. */
+int xsd_test_gconv(int cout, int cin, const float* dev_params, long long param_off, int transposed, const xsd_test_gconv_args* host_args,
+                   int B, int H, int W, int* host_path, void* stream);
+/* dev_grads: flat gradient buffer laid out like dev_params (dw at param_off, db behind it; nothing else is written).
+ * *host_parts: the number of partial sums the net's rule chose. */
+int xsd_test_gwgrad(int cout, int cin, long long param_off, const float* dev_x, long long xbs, const float* dev_g, long long gbs,
+                    float* dev_grads, int B, int H, int W, int* host_path, int* host_parts, void* stream);
+/* The net's elementwise launches over [B][C][H * W] views.  op 0: d = a * s; 1: d += a * s; 2: d = s > 0 ? d : d * a (dbs / sbs: batch strides);
+ * 3: d[B][C][H][W] = unshuffle(s = dU, s2 = U: [B][C / 4][2H][2W]) with d = U > 0 ? dU : dU * a; 4: d[B][H * W] += sum over the C channels
+ * of s[B][C][H * W]; 5: d = (0 <= s <= 1) ? s2 : 0 over B * C * H * W elements (s = pre, s2 = dy). */
+int xsd_test_gop(int op, float* dev_d, long long dbs, const float* dev_s, long long sbs, const float* dev_s2, int B, int C, int H, int W,
+                 float a, void* stream);
+/* Packs a table of n convs (at most 8; parameters from offset 0 of dev_params, conv after conv: weight, bias) with the net's pack() and
+ * copies the transposed buffer and the block-packed buffer out (either may be NULL; capacities in floats).  host_off[3 i + 0 .. 2]:
+ * conv i's offsets in wt, and in wblk of its forward and its input-gradient blocks (-1: none); host_count[0 .. 1]: floats of wt and wblk. */
+int xsd_test_gpack(int n, const int* host_cout, const int* host_cin, const float* dev_params, float* dev_wt, long long wt_cap,
+                   float* dev_wblk, long long wblk_cap, long long* host_off, long long* host_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,63 @@ def guarded_planes(n, B, H, W, fill, guard_px=4096):
     return planes, check
 
 
+def guarded_flat(items, guard=4096):
+    """Flat float32 buffers carved out of ONE allocation with NaN guard bands in front of, between and behind them (the flat-buffer
+    sibling of guarded_planes).  An item is a size (the buffer starts as NaN: an output) or a numpy array (copied in).  Every buffer
+    starts 256-byte aligned; the padding behind it counts as guard band.  Returns (views, check)."""
+    sizes = [int(it) if np.isscalar(it) else int(np.asarray(it).size) for it in items]
+    starts, off = [], guard
+    for sz in sizes:
+        starts.append(off)
+        off = (off + sz + 63) // 64 * 64 + guard
+    buf = torch.full((off,), float("nan"), device="cuda")
+    views = []
+    for it, st, sz in zip(items, starts, sizes):
+        v = buf[st:st + sz]
+        if not np.isscalar(it):
+            v.copy_(torch.from_numpy(np.ascontiguousarray(it, dtype=np.float32).reshape(-1)))
+        views.append(v)
+    bands = [(0, guard)] + [(st + sz, (starts[i + 1] if i + 1 < len(starts) else off)) for i, (st, sz) in enumerate(zip(starts, sizes))]
+
+    def check():
+        for i, (a, b) in enumerate(bands):
+            assert bool(torch.isnan(buf[a:b]).all()), f"guard band {i} was written"
+    return views, check
+
+
+def guarded_nchw(items, guard=4096):
+    """The NCHW sibling: an item is a shape (NaN-filled) or a numpy array of any rank; the views come back in that shape."""
+    shapes = [tuple(it) if isinstance(it, (tuple, list)) else np.asarray(it).shape for it in items]
+    flat, check = guarded_flat([int(np.prod(s)) if isinstance(it, (tuple, list)) else it for it, s in zip(items, shapes)], guard)
+    return [v.view(*s) for v, s in zip(flat, shapes)], check
+
+
+class Guarded:
+    """Named device tensors between guard bands (guarded_nchw) that remember what they held: `ro` names the tensors a launch may only
+    read.  check() asserts the guard bands and that every read-only tensor came back bit for bit (NaN payloads included)."""
+
+    def __init__(self, ro=(), **items):
+        self.names = list(items)
+        views, self._check = guarded_nchw([items[k] for k in self.names])
+        self.t = dict(zip(self.names, views))
+        self.ro = tuple(ro)
+        self.before = {k: v.clone() for k, v in self.t.items()}
+
+    def ptr(self, name, offset=0):
+        return self.t[name].data_ptr() + 4 * int(offset) if name in self.t else None
+
+    def np(self, name):
+        return self.t[name].cpu().numpy()
+
+    def same_bits(self, name):
+        return torch.equal(self.t[name].view(torch.int32), self.before[name].view(torch.int32))
+
+    def check(self, untouched=()):
+        self._check()
+        for k in tuple(self.ro) + tuple(untouched):
+            assert self.same_bits(k), f"{k} was modified"
+
+
 def flip_candidates(kind, blocks, state, x, t, nup=1, eps=4e-6, return_clamp_mask=False, device="cpu"):
     """Where can two fp32-accurate implementations legitimately take different branches of the network's step functions?
     A float64 evaluation of the reference graph (rrdb_blocks.py:37-54, generator_rrdb.py:66-137) records, for every conv

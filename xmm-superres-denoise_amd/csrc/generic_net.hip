@@ -509,6 +509,40 @@ GenericNet::~GenericNet()
     hipFree(wt); hipFree(wblk); hipFree(descs_dev); hipFree(ws); hipFree(wg_partial); hipFree(wg_bias_partial);
 }
 
+// The conv table of a net: flat-parameter, transposed-copy and block-packed offsets in creation order, one pack descriptor per conv
+// (create() and the tests' create_convs() both build theirs here and allocate through gtable_alloc)
+struct GTable {
+    long long off = 0, toff = 0, boff = 0;
+    std::vector<GPackDesc> d;
+    GConvW mk(int co, int ci)
+    {
+        GConvW c; c.w = off; off += (long long)co * ci * 9; c.b = off; off += co; c.cout = co; c.cin = ci; c.t = toff; toff += (long long)co * ci * 9;
+        c.pf = c.pt = -1;
+        if (c.wide()) {      // block-packed copies for the MFMA kernels: the conv and its input-gradient conv
+            const long long blk = (long long)((co + 31) / 32) * ((ci + 31) / 32) * 9 * 1024;
+            c.pf = boff; boff += blk; c.pt = boff; boff += blk;
+        }
+        GPackDesc q; q.w_off = c.w; q.t_off = c.t; q.pf_off = c.pf; q.pt_off = c.pt; q.cout = c.cout; q.cin = c.cin; d.push_back(q);
+        return c;
+    }
+};
+static bool gtable_alloc(GenericNet* n, const GTable& t)
+{
+    n->nparams = t.off;
+    n->wt_floats = t.toff;
+    n->ndesc = (int)t.d.size();
+    int maxw = 0;
+    for (auto& q : t.d) maxw = std::max(maxw, q.cout * q.cin * 9);
+    n->max_w = maxw;
+    n->wblk_floats = t.boff;
+    return hipMalloc((void**)&n->wt, sizeof(float) * t.toff) == hipSuccess &&
+           (!t.boff || hipMalloc((void**)&n->wblk, sizeof(float) * t.boff) == hipSuccess) &&
+           hipMalloc((void**)&n->descs_dev, sizeof(GPackDesc) * t.d.size()) == hipSuccess &&
+           hipMemcpy(n->descs_dev, t.d.data(), sizeof(GPackDesc) * t.d.size(), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMalloc((void**)&n->wg_partial, sizeof(float) * (size_t)GenericNet::MAX_PARTS * maxw) == hipSuccess &&
+           hipMalloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) == hipSuccess;   // parts * cout <= capacity / (9 cin)
+}
+
 GenericNet* GenericNet::create(const xsd_config& cfg)
 {
     GenericNet* n = new GenericNet();
@@ -516,16 +550,9 @@ GenericNet* GenericNet::create(const xsd_config& cfg)
     n->nf = cfg.num_filters; n->cin = cfg.in_channels; n->cout = cfg.out_channels; n->blocks = cfg.num_res_blocks;
     n->sr = cfg.kind == XSD_KIND_SR;
     n->nup = n->sr ? cfg.num_upsample : 0;
-    long long off = 0, toff = 0, boff = 0;
-    auto mk = [&](int co, int ci) {
-        GConvW c; c.w = off; off += (long long)co * ci * 9; c.b = off; off += co; c.cout = co; c.cin = ci; c.t = toff; toff += (long long)co * ci * 9;
-        c.pf = c.pt = -1;
-        if (c.wide()) {      // block-packed copies for the MFMA kernels: the conv and its input-gradient conv
-            const long long blk = (long long)((co + 31) / 32) * ((ci + 31) / 32) * 9 * 1024;
-            c.pf = boff; boff += blk; c.pt = boff; boff += blk;
-        }
-        return c;
-    };
+    GTable t;
+    long long& off = t.off;
+    auto mk = [&](int co, int ci) { return t.mk(co, ci); };
     n->first = mk(n->nf, n->cin);
     for (int i = 0; i < n->blocks; ++i) {
         n->rrdb_begin.push_back(off);
@@ -537,26 +564,22 @@ GenericNet* GenericNet::create(const xsd_config& cfg)
     n->last = mk(n->cout, n->nf);
     for (int u = 0; u < n->nup; ++u) n->up.push_back(mk(4 * n->nf, n->nf));
     if (n->sr) n->hr = mk(n->nf, n->nf);
-    n->nparams = off;
-    n->wt_floats = toff;
-    std::vector<GPackDesc> d;
-    auto add = [&](const GConvW& c) { GPackDesc q; q.w_off = c.w; q.t_off = c.t; q.pf_off = c.pf; q.pt_off = c.pt; q.cout = c.cout; q.cin = c.cin; d.push_back(q); };
-    add(n->first);
-    for (auto& c : n->rdb) add(c);
-    add(n->trunk); add(n->last);
-    for (auto& c : n->up) add(c);
-    if (n->sr) add(n->hr);
-    n->ndesc = (int)d.size();
-    int maxw = 0;
-    for (auto& q : d) maxw = std::max(maxw, q.cout * q.cin * 9);
-    n->max_w = maxw;
-    n->wblk_floats = boff;
-    if (hipMalloc((void**)&n->wt, sizeof(float) * toff) != hipSuccess ||
-        (boff && hipMalloc((void**)&n->wblk, sizeof(float) * boff) != hipSuccess) ||
-        hipMalloc((void**)&n->descs_dev, sizeof(GPackDesc) * d.size()) != hipSuccess ||
-        hipMemcpy(n->descs_dev, d.data(), sizeof(GPackDesc) * d.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc((void**)&n->wg_partial, sizeof(float) * (size_t)GenericNet::MAX_PARTS * maxw) != hipSuccess ||
-        hipMalloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) != hipSuccess) {   // parts * cout <= capacity / (9 cin)
+    // (the pack descriptors stand in creation order, which is the order the table was always in: first, dense blocks, trunk, last, up, hr)
+    if (!gtable_alloc(n, t)) {
+        delete n;
+        return nullptr;
+    }
+    return n;
+}
+
+GenericNet* GenericNet::create_convs(int nconv, const int* couts, const int* cins, long long param_off)
+{
+    GenericNet* n = new GenericNet();
+    memset(&n->cfg, 0, sizeof(n->cfg));
+    GTable t;
+    t.off = param_off;
+    for (int i = 0; i < nconv; ++i) n->convs.push_back(t.mk(couts[i], cins[i]));
+    if (!gtable_alloc(n, t)) {
         delete n;
         return nullptr;
     }
@@ -632,11 +655,13 @@ hipError_t GenericNet::conv(hipStream_t s, const GConvW& c, bool transposed, con
     if (tweak) tweak(&p);
     if (c.wide() && (long long)H_ * W_ * 32 * 4 < (1ll << 31)) {      // at least 16 channels on both sides: the fp32 matrix instruction (32-bit byte offsets inside a 32-channel block)
         p.w = wblk + (transposed ? c.pt : c.pf);
+        last_path = 2;
         GCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gconv_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GM_LDS_BYTES));
         const int tiles = ((W_ + GW_COLS - 1) / GW_COLS) * ((H_ + GW_ROWS - 1) / GW_ROWS);
         hipLaunchKernelGGL(gconv_mfma_kernel, dim3(tiles, (p.cout + 31) / 32, B_), dim3(256), GM_LDS_BYTES, s, p);
         return hipGetLastError();
     }
+    last_path = 1;
     const int tiles = ((W_ + GT - 1) / GT) * ((H_ + GT - 1) / GT);
     hipLaunchKernelGGL(gconv3x3_kernel, dim3(tiles, (p.cout + GCO - 1) / GCO, B_), dim3(256), 0, s, p);
     return hipGetLastError();
@@ -656,14 +681,17 @@ hipError_t GenericNet::wgrad(hipStream_t s, const GConvW& c, const float* x, lon
         // enough workgroups for two per CU and a few rounds of them, at least four tiles each
         parts = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(cap, 2048), std::min<long long>(tiles / 4, (2048 + blocks - 1) / blocks)));
         p.parts = parts;
+        last_path = 2;
         GCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gwgrad_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GW_LDS_BYTES));
         hipLaunchKernelGGL(gwgrad_mfma_kernel, dim3(blocks, parts), dim3(256), GW_LDS_BYTES, s, p);
     } else {
         const long long N = (long long)B_ * H_ * W_;
         parts = (int)std::min<long long>(std::min<long long>(cap, MAX_PARTS), std::max<long long>(1, N / 2048));
         p.parts = parts;
+        last_path = 1;
         hipLaunchKernelGGL(gwgrad_direct_kernel, dim3(c.cin, c.cout, parts), dim3(256), 0, s, p);
     }
+    last_parts = parts;
     const int n = c.cout * c.cin * 9;
     hipLaunchKernelGGL(gwgrad_reduce_kernel, dim3((std::max(n, c.cout) + 255) / 256), dim3(256), 0, s, wg_partial, wg_bias_partial, parts, c.cout, c.cin,
                        grads + c.w, grads + c.b);
@@ -673,6 +701,22 @@ hipError_t GenericNet::wgrad(hipStream_t s, const GConvW& c, const float* x, lon
 hipError_t GenericNet::ew(hipStream_t s, int op, float* d, long long dbs, const float* src, long long sbs, int C, long long HW, float a)
 {
     hipLaunchKernelGGL(gew_kernel, dim3(ew_grid((long long)B * C * HW)), dim3(256), 0, s, op, d, dbs, src, sbs, C, HW, B, a);
+    return hipGetLastError();
+}
+
+hipError_t GenericNet::unshuffle(hipStream_t s, const float* dU, const float* U_, float* G, int B_, int C4, int H_, int W_, float slope)
+{
+    hipLaunchKernelGGL(gunshuffle_kernel, dim3(ew_grid((long long)B_ * C4 * H_ * W_)), dim3(256), 0, s, dU, U_, G, B_, C4, H_, W_, slope);
+    return hipGetLastError();
+}
+hipError_t GenericNet::sum_channels(hipStream_t s, float* d, const float* src, int C, long long HW, int B_)
+{
+    hipLaunchKernelGGL(gsum_channels_kernel, dim3(ew_grid((long long)B_ * HW)), dim3(256), 0, s, d, src, C, HW, B_);
+    return hipGetLastError();
+}
+hipError_t GenericNet::clamp_bwd(hipStream_t s, const float* pre_, const float* dy, float* dpre_, long long n)
+{
+    hipLaunchKernelGGL(gclamp_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, s, pre_, dy, dpre_, n);
     return hipGetLastError();
 }
 
@@ -754,7 +798,7 @@ hipError_t GenericNet::backward_stage(int stage, const float* dy, float* dx, flo
     const long long HWo = HW << (2 * lv);
     const int Ho = H << lv, Wo = W << lv;
     if (stage == 0) {
-        hipLaunchKernelGGL(gclamp_bwd_kernel, dim3(ew_grid((long long)B * cout * HWo)), dim3(256), 0, s, pre, dy, dpre, (long long)B * cout * HWo);
+        GCHK(clamp_bwd(s, pre, dy, dpre, (long long)B * cout * HWo));
         const float* feat = sr ? H1 : T;
         GCHK(wgrad(s, last, feat, nf * HWo, dpre, cout * HWo, B, Ho, Wo, grads));
         if (!sr) {
@@ -772,7 +816,7 @@ hipError_t GenericNet::backward_stage(int stage, const float* dy, float* dx, flo
             for (int u = nup - 1; u >= 0; --u) {
                 const long long HWu = HW << (2 * u);
                 const int Hu = H << u, Wu = W << u;
-                hipLaunchKernelGGL(gunshuffle_kernel, dim3(ew_grid((long long)B * 4 * nf * HWu)), dim3(256), 0, s, (const float*)dU, (const float*)U[u], gup, B, 4 * nf, Hu, Wu, 0.01f);
+                GCHK(unshuffle(s, dU, U[u], gup, B, 4 * nf, Hu, Wu, 0.01f));
                 const float* xin = u > 0 ? U[u - 1] : T;
                 GCHK(wgrad(s, up[u], xin, nf * HWu, gup, 4 * nf * HWu, B, Hu, Wu, grads));
                 float* dn_ = u > 0 ? (dU == dHi[1] ? dHi[0] : dHi[1]) : dT;
@@ -809,7 +853,7 @@ hipError_t GenericNet::backward_stage(int stage, const float* dy, float* dx, flo
         GCHK(conv(s, first, true, dRR, nfHW, dx, cin * HW, B, H, W, nullptr));
         if (!sr) {      // skip path of the DN head: d(x) += d(out) (summed over the output channels when x broadcasts)
             if (cin == cout) GCHK(ew(s, 1, dx, cin * HW, dpre, cout * HW, cin, HW, 1.f));
-            else hipLaunchKernelGGL(gsum_channels_kernel, dim3(ew_grid((long long)B * HW)), dim3(256), 0, s, dx, (const float*)dpre, cout, HW, B);
+            else GCHK(sum_channels(s, dx, dpre, cout, HW, B));
         }
     }
     return hipGetLastError();
@@ -822,6 +866,41 @@ void GenericNet::grad_range(int stage, long long* off, long long* cnt) const
     else if (stage <= blocks) { const int i = blocks - stage; a = rrdb_begin[i]; b = rrdb_begin[i + 1]; }
     else { a = 0; b = rrdb_begin[0]; }
     *off = a; *cnt = b - a;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// test access (generic_net.h): the private launchers by name, nothing restated
+// ---------------------------------------------------------------------------------------------------------------
+hipError_t GenericNet::test_conv(hipStream_t s, int i, bool transposed, const xsd_test_gconv_args& a, int B_, int H_, int W_)
+{
+    return conv(s, convs[i], transposed, a.x, a.xbs, a.y, a.ybs, B_, H_, W_, [&a](void* q) {
+        GConvP* p = (GConvP*)q;
+        p->a1 = a.a1; p->e1 = a.e1; p->e1bs = a.e1bs; p->s1 = a.s1; p->e1c = a.e1c;
+        p->a2 = a.a2; p->e2 = a.e2; p->e2bs = a.e2bs; p->s2 = a.s2;
+        p->slope = a.slope; p->accumulate = a.accumulate; p->shuffle = a.shuffle;
+        p->skip = a.skip; p->skipbs = a.skipbs; p->skipc = a.skipc; p->pre = a.pre; p->clamp01 = a.clamp01;
+    });
+}
+hipError_t GenericNet::test_wgrad(hipStream_t s, int i, const float* x, long long xbs, const float* g, long long gbs, int B_, int H_, int W_, float* grads)
+{
+    return wgrad(s, convs[i], x, xbs, g, gbs, B_, H_, W_, grads);
+}
+hipError_t GenericNet::test_op(hipStream_t s, int op, float* d, long long dbs, const float* src, long long sbs, const float* src2, int B_, int C, int H_, int W_, float a)
+{
+    const long long HW = (long long)H_ * W_;
+    switch (op) {
+    case 0: case 1: case 2: {
+        const int keep = B;
+        B = B_;                                 // ew() sizes its launch by the planned batch
+        const hipError_t err = ew(s, op, d, dbs, src, sbs, C, HW, a);
+        B = keep;
+        return err;
+    }
+    case 3: return unshuffle(s, src, src2, d, B_, C, H_, W_, a);
+    case 4: return sum_channels(s, d, src, C, HW, B_);
+    case 5: return clamp_bwd(s, src, src2, d, (long long)B_ * C * HW);
+    }
+    return hipErrorInvalidValue;
 }
 
 } // namespace xsd

@@ -178,6 +178,10 @@ static int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
     return e->nparts;
 }
 
+// Workgroups (partial sums) of one edge weight-gradient launch: the plan and the single-launch test hook (xsd_test_edge_wgrad) both ask
+// here.  A constant: the kernel strides over the image rows, idle workgroups store zeros, edge_partial holds this many records.
+static int edge_wgrad_nblocks() { return EDGE_WGRAD_BLOCKS; }
+
 // Profile classes of xsd_profile_read (include/xsd.h): 0 conv (forward + input-gradient), 1 weight gradient; the HBM-bound kernels:
 // 2 edge_expand (1 -> 32), 3 edge_reduce (32 -> 1), 4 edge_wgrad, 5 L1 loss, 6 Adam, 7 clamp backward, 8 plane max |x| sweeps.
 // `bytes` is ALGORITHMIC traffic (SURVEY 8d rule: every operand once), `flop` 2 x MAC.
@@ -728,7 +732,7 @@ struct Builder {
             for (int co = 0; co < CO; ++co)
             for (int q = 0; q < P; ++q) { // conv_last weight grad, 32 input channels of one output channel per launch (the bias gradient is the same sum every time)
                 EdgeWgradParams p; memset(&p, 0, sizeof(p));
-                p.B = B; p.H = H << lo; p.W = W << lo; p.f = headf[q]; p.s = dpre + co * HWo; p.s_bs = CO * HWo; p.nblocks = EDGE_WGRAD_BLOCKS;
+                p.B = B; p.H = H << lo; p.W = W << lo; p.f = headf[q]; p.s = dpre + co * HWo; p.s_bs = CO * HWo; p.nblocks = edge_wgrad_nblocks();
                 const long long wo = e->last_w + ((long long)co * 32 * P + 32 * q) * 9, bo = e->last_b + co;
                 S.push_back([eng, p, wo, bo](hipStream_t s) mutable {
                     p.partial = eng->edge_partial; return run_edge_wgrad(eng, p, 1, eng->b_grads + wo, eng->b_grads + bo, s);
@@ -840,7 +844,7 @@ struct Builder {
             for (int ch = 0; ch < CI; ++ch)
                 for (int q = 0; q < P; ++q) {
                     EdgeWgradParams p; memset(&p, 0, sizeof(p));
-                    p.B = B; p.H = H; p.W = W; p.f = dFea[q]; p.nblocks = EDGE_WGRAD_BLOCKS; p.s_bs = CI * HW;
+                    p.B = B; p.H = H; p.W = W; p.f = dFea[q]; p.nblocks = edge_wgrad_nblocks(); p.s_bs = CI * HW;
                     const long long wo = e->first_w + ((long long)32 * q * CI + ch) * 9, bo = e->first_b + 32 * q, xo = ch * HW;
                     const int cstride = 9 * CI;
                     S.push_back([eng, p, wo, bo, xo, cstride](hipStream_t s) mutable {
@@ -1661,6 +1665,175 @@ int xsd_test_wgrad_ex(xsd_engine* e, const float* const* x_planes, int n_in, con
     }
     if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
     if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+// ---- the edge layers one by one (include/xsd.h): the engine's packer, the engine's launchers, the engine's block-count rule ----
+// one (32, 9) block through pack_edge_kernel; *packed = the form asked for ([tap][c]), *base = the allocation to free
+static int edge_pack_one(const float* dev_w, int w_last, int flipped, int first_cstride, hipStream_t s, const float** packed, float** base)
+{
+    if (!dev_w) return fail(XSD_ERR_ARG, "null weight block");
+    if (!w_last && first_cstride < 9) return fail(XSD_ERR_ARG, "first_cstride is 9 * in_channels");
+    float* buf = nullptr;
+    if (hipMalloc((void**)&buf, sizeof(float) * 4 * 288) != hipSuccess) return fail(XSD_ERR_NOMEM, "edge weight forms");
+    hipError_t err = launch_pack_edge(w_last ? nullptr : dev_w, w_last ? dev_w : nullptr, buf, buf + 288, buf + 576, buf + 864, s, w_last ? 9 : first_cstride);
+    if (err != hipSuccess) { hipFree(buf); return fail(XSD_ERR_HIP, "pack_edge launch: %s", hipGetErrorString(err)); }
+    *packed = buf + (w_last ? 576 : 0) + (flipped ? 288 : 0);
+    *base = buf;
+    return XSD_OK;
+}
+static int edge_hook_args(const xsd_engine* e, int B, int H, int W)
+{
+    if (!e || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null engine or empty shape");
+    if (e->generic) return fail(XSD_ERR_ARG, "the edge kernels belong to the plane path");
+    if (W > EDGE_MAX_W) return fail(XSD_ERR_ARG, "the edge kernels stage rows of at most %d pixels", EDGE_MAX_W);
+    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large");
+    return XSD_OK;
+}
+
+int xsd_test_edge_expand(xsd_engine* e, const float* dev_s, long long s_bs, const float* dev_w, int w_last, int flipped, int first_cstride,
+                         const float* dev_bias, float* dev_out, const float* dev_mask, float mslope, const unsigned short* dev_bits,
+                         int accumulate, float* dev_amax, int B, int H, int W, void* stream)
+{
+    int rc = edge_hook_args(e, B, H, W);
+    if (rc) return rc;
+    if (!dev_s || !dev_out || s_bs < 0) return fail(XSD_ERR_ARG, "null image / output plane or negative stride");
+    hipStream_t s = (hipStream_t)stream;
+    const float* packed = nullptr; float* base = nullptr;
+    if ((rc = edge_pack_one(dev_w, w_last, flipped, first_cstride, s, &packed, &base))) return rc;
+    EdgeExpandParams p; memset(&p, 0, sizeof(p));
+    p.B = B; p.H = H; p.W = W; p.s = dev_s; p.s_bs = s_bs; p.w = packed; p.bias = dev_bias; p.out = dev_out;
+    p.mask = dev_mask; p.mslope = mslope; p.bits = dev_bits; p.accumulate = accumulate; p.amax = dev_amax;
+    hipError_t err = launch_edge_expand(p, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    hipFree(base);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_expand launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_edge_reduce(xsd_engine* e, const float* dev_f, const float* dev_w, int w_last, int flipped, int first_cstride,
+                         const float* dev_bias, const float* dev_skip, long long skip_bs, float* dev_pre, float* dev_y, long long y_bs,
+                         int clamp01, const float* dev_addto, int B, int H, int W, void* stream)
+{
+    int rc = edge_hook_args(e, B, H, W);
+    if (rc) return rc;
+    if (!dev_f || !dev_y || skip_bs < 0 || y_bs < 0) return fail(XSD_ERR_ARG, "null feature plane / output or negative stride");
+    hipStream_t s = (hipStream_t)stream;
+    const float* packed = nullptr; float* base = nullptr;
+    if ((rc = edge_pack_one(dev_w, w_last, flipped, first_cstride, s, &packed, &base))) return rc;
+    EdgeReduceParams p; memset(&p, 0, sizeof(p));
+    p.B = B; p.H = H; p.W = W; p.f = dev_f; p.w = packed; p.bias = dev_bias; p.skip = dev_skip; p.skip_bs = skip_bs;
+    p.pre = dev_pre; p.y = dev_y; p.y_bs = y_bs; p.clamp01 = clamp01; p.addto = dev_addto;
+    hipError_t err = launch_edge_reduce(p, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    hipFree(base);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_reduce launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_edge_wgrad(xsd_engine* e, const float* dev_f, const float* dev_s, long long s_bs, int mode, float* dev_dw, float* dev_db,
+                        int cstride, int nblocks, int* host_nblocks, int B, int H, int W, void* stream)
+{
+    int rc = edge_hook_args(e, B, H, W);
+    if (rc) return rc;
+    if (!dev_f || !dev_s || !dev_dw || !dev_db || s_bs < 0) return fail(XSD_ERR_ARG, "null argument or negative stride");
+    if (mode != 0 && mode != 1) return fail(XSD_ERR_ARG, "mode 0 (conv_first) or 1 (conv_last)");
+    if (cstride < 9) return fail(XSD_ERR_ARG, "cstride is 9 * in_channels");
+    const int rule = edge_wgrad_nblocks();
+    if (nblocks < 0 || nblocks > rule) return fail(XSD_ERR_ARG, "at most %d workgroups (the partial-sum buffer)", rule);
+    hipStream_t s = (hipStream_t)stream;
+    EdgeWgradParams p; memset(&p, 0, sizeof(p));
+    p.B = B; p.H = H; p.W = W; p.f = dev_f; p.s = dev_s; p.s_bs = s_bs; p.partial = e->edge_partial; p.nblocks = nblocks ? nblocks : rule;
+    if (host_nblocks) *host_nblocks = p.nblocks;
+    hipError_t err = launch_edge_wgrad(p, mode, dev_dw, dev_db, s, cstride);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_wgrad launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+// ---- the generic-width kernels one by one (include/xsd.h): a GenericNet of one conv, its own pack() / conv() / wgrad() / ew() ----
+static int gconv_hook_args(int cout, int cin, long long param_off, int B, int H, int W)
+{
+    if (cout < 1 || cin < 1 || cout > 4096 || cin > 4096 || param_off < 0 || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "bad channel counts, offset or shape");
+    if ((long long)H * W > (1ll << 24) || (long long)B * H * W > (1ll << 26)) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
+    return XSD_OK;
+}
+
+int xsd_test_gconv(int cout, int cin, const float* dev_params, long long param_off, int transposed, const xsd_test_gconv_args* a,
+                   int B, int H, int W, int* host_path, void* stream)
+{
+    int rc = gconv_hook_args(cout, cin, param_off, B, H, W);
+    if (rc) return rc;
+    if (!dev_params || !a || !a->x || !a->y) return fail(XSD_ERR_ARG, "null argument");
+    if (a->shuffle && ((transposed ? cin : cout) & 3)) return fail(XSD_ERR_ARG, "a pixel-shuffled output has a multiple of four channels");
+    if (a->e1 && (a->e1c < 0 || a->e1c > (transposed ? cin : cout))) return fail(XSD_ERR_ARG, "e1c lies outside the output channels");
+    if (a->skip && a->skipc != 1 && a->skipc != (transposed ? cin : cout)) return fail(XSD_ERR_ARG, "skipc is 1 or the output channel count");
+    hipStream_t s = (hipStream_t)stream;
+    GenericNet* n = GenericNet::create_convs(1, &cout, &cin, param_off);
+    if (!n) return fail(XSD_ERR_NOMEM, "generic-width conv: device allocation failed");
+    hipError_t err = n->pack(dev_params, s);
+    if (err == hipSuccess) err = n->test_conv(s, 0, transposed != 0, *a, B, H, W);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (host_path) *host_path = n->last_path;
+    delete n;
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width conv: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_gwgrad(int cout, int cin, long long param_off, const float* dev_x, long long xbs, const float* dev_g, long long gbs,
+                    float* dev_grads, int B, int H, int W, int* host_path, int* host_parts, void* stream)
+{
+    int rc = gconv_hook_args(cout, cin, param_off, B, H, W);
+    if (rc) return rc;
+    if (!dev_x || !dev_g || !dev_grads) return fail(XSD_ERR_ARG, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    GenericNet* n = GenericNet::create_convs(1, &cout, &cin, param_off);
+    if (!n) return fail(XSD_ERR_NOMEM, "generic-width weight gradient: device allocation failed");
+    hipError_t err = n->test_wgrad(s, 0, dev_x, xbs, dev_g, gbs, B, H, W, dev_grads);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (host_path) *host_path = n->last_path;
+    if (host_parts) *host_parts = n->last_parts;
+    delete n;
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width weight gradient: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_gop(int op, float* dev_d, long long dbs, const float* dev_s, long long sbs, const float* dev_s2, int B, int C, int H, int W,
+                 float a, void* stream)
+{
+    if (op < 0 || op > 5 || !dev_d || !dev_s || B < 1 || C < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "bad op, null argument or empty shape");
+    if ((op == 3 || op == 5) && !dev_s2) return fail(XSD_ERR_ARG, "op %d reads a second tensor", op);
+    if (op == 3 && (C & 3)) return fail(XSD_ERR_ARG, "the unshuffle writes a multiple of four channels");
+    if ((long long)B * C * H * W > (1ll << 28)) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
+    hipStream_t s = (hipStream_t)stream;
+    const int one = 1;
+    GenericNet* n = GenericNet::create_convs(1, &one, &one, 0);
+    if (!n) return fail(XSD_ERR_NOMEM, "generic-width op: device allocation failed");
+    hipError_t err = n->test_op(s, op, dev_d, dbs, dev_s, sbs, dev_s2, B, C, H, W, a);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    delete n;
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width op %d: %s", op, hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_gpack(int nconv, const int* host_cout, const int* host_cin, const float* dev_params, float* dev_wt, long long wt_cap,
+                   float* dev_wblk, long long wblk_cap, long long* host_off, long long* host_count, void* stream)
+{
+    if (nconv < 1 || nconv > 8 || !host_cout || !host_cin || !dev_params || !host_off || !host_count) return fail(XSD_ERR_ARG, "bad table or null argument");
+    for (int i = 0; i < nconv; ++i)
+        if (host_cout[i] < 1 || host_cin[i] < 1 || host_cout[i] > 4096 || host_cin[i] > 4096) return fail(XSD_ERR_ARG, "bad channel counts");
+    hipStream_t s = (hipStream_t)stream;
+    GenericNet* n = GenericNet::create_convs(nconv, host_cout, host_cin, 0);
+    if (!n) return fail(XSD_ERR_NOMEM, "generic-width pack: device allocation failed");
+    for (int i = 0; i < nconv; ++i) { host_off[3 * i] = n->convs[i].t; host_off[3 * i + 1] = n->convs[i].pf; host_off[3 * i + 2] = n->convs[i].pt; }
+    host_count[0] = n->wt_floats; host_count[1] = n->wblk_floats;
+    if ((dev_wt && wt_cap < n->wt_floats) || (dev_wblk && wblk_cap < n->wblk_floats)) { delete n; return fail(XSD_ERR_ARG, "a read-back buffer is too small"); }
+    hipError_t err = n->pack(dev_params, s);
+    if (err == hipSuccess && dev_wt) err = hipMemcpyAsync(dev_wt, n->wt, sizeof(float) * n->wt_floats, hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess && dev_wblk && n->wblk_floats) err = hipMemcpyAsync(dev_wblk, n->wblk, sizeof(float) * n->wblk_floats, hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    delete n;
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width pack: %s", hipGetErrorString(err));
     return XSD_OK;
 }
 

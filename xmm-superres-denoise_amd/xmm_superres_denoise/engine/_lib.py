@@ -29,6 +29,15 @@ class XsdTestOut(ctypes.Structure):      # xsd_test_out (include/xsd.h): one out
                 ("bits_out", ctypes.c_void_p), ("bits_in", ctypes.c_void_p)]
 
 
+class XsdTestGconvArgs(ctypes.Structure):      # xsd_test_gconv_args (include/xsd.h): the views and the fused epilogue of one generic-width conv
+    _fields_ = [("x", ctypes.c_void_p), ("xbs", ctypes.c_int64), ("y", ctypes.c_void_p), ("ybs", ctypes.c_int64),
+                ("a1", ctypes.c_float), ("e1", ctypes.c_void_p), ("e1bs", ctypes.c_int64), ("s1", ctypes.c_float), ("e1c", ctypes.c_int32),
+                ("a2", ctypes.c_float), ("e2", ctypes.c_void_p), ("e2bs", ctypes.c_int64), ("s2", ctypes.c_float),
+                ("slope", ctypes.c_float), ("accumulate", ctypes.c_int32), ("shuffle", ctypes.c_int32),
+                ("skip", ctypes.c_void_p), ("skipbs", ctypes.c_int64), ("skipc", ctypes.c_int32),
+                ("pre", ctypes.c_void_p), ("clamp01", ctypes.c_int32)]
+
+
 class XsdRestormerConfig(ctypes.Structure):
     _fields_ = [("inp_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("dim", ctypes.c_int32),
                 ("num_blocks", ctypes.c_int32 * 4), ("num_refinement_blocks", ctypes.c_int32), ("heads", ctypes.c_int32 * 4),
@@ -123,6 +132,14 @@ def load():
     L.xsd_test_conv3x3_bwd.argtypes = [vp, ctypes.POINTER(vp), i32, fp, fp, ctypes.POINTER(vp), fp, fp, i32, i32, i32, vp]
     L.xsd_test_conv3x3_ex.argtypes = [vp, ctypes.POINTER(vp), i32, i32, fp, fp, ctypes.POINTER(XsdTestOut), i32, i32, ctypes.POINTER(f32), i32, i32, i32, vp]
     L.xsd_test_wgrad_ex.argtypes = [vp, ctypes.POINTER(vp), i32, ctypes.POINTER(vp), i32, i32, f32, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, vp]
+    ip = ctypes.POINTER(i32)
+    L.xsd_test_edge_expand.argtypes = [vp, fp, i64, fp, i32, i32, i32, fp, fp, fp, f32, vp, i32, fp, i32, i32, i32, vp]
+    L.xsd_test_edge_reduce.argtypes = [vp, fp, fp, i32, i32, i32, fp, fp, i64, fp, fp, i64, i32, fp, i32, i32, i32, vp]
+    L.xsd_test_edge_wgrad.argtypes = [vp, fp, fp, i64, i32, fp, fp, i32, i32, ip, i32, i32, i32, vp]
+    L.xsd_test_gconv.argtypes = [i32, i32, fp, i64, i32, ctypes.POINTER(XsdTestGconvArgs), i32, i32, i32, ip, vp]
+    L.xsd_test_gwgrad.argtypes = [i32, i32, i64, fp, i64, fp, i64, fp, i32, i32, i32, ip, ip, vp]
+    L.xsd_test_gop.argtypes = [i32, fp, i64, fp, i64, fp, i32, i32, i32, i32, f32, vp]
+    L.xsd_test_gpack.argtypes = [i32, ip, ip, fp, fp, i64, fp, i64, ctypes.POINTER(i64), ctypes.POINTER(i64), vp]
     L.xsd_restormer_create.argtypes = [ctypes.POINTER(XsdRestormerConfig), ctypes.POINTER(vp)]
     L.xsd_restormer_destroy.argtypes = [vp]
     L.xsd_restormer_destroy.restype = None
@@ -197,6 +214,7 @@ ABI_SYMBOLS = [
     "xsd_forward", "xsd_backward", "xsd_backward_num_stages", "xsd_backward_stage", "xsd_grad_range",
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_ext_metrics_create", "xsd_ext_metrics_destroy", "xsd_ext_metrics_eval", "xsd_fsim_create", "xsd_fsim_destroy", "xsd_fsim_eval", "xsd_fsim_test_dft2", "xsd_fsim_test_median", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_compose_batch", "xsd_normalize", "xsd_image_upsample",
     "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd", "xsd_test_conv3x3_ex", "xsd_test_wgrad_ex",
+    "xsd_test_edge_expand", "xsd_test_edge_reduce", "xsd_test_edge_wgrad", "xsd_test_gconv", "xsd_test_gwgrad", "xsd_test_gop", "xsd_test_gpack",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
