@@ -586,8 +586,8 @@ int xsd_probe_mfma_stream(int fmt, double seconds, double* mfma_tflops, double* 
  * [17] MFMA walk, [18] MFMA wave at the barrier, [19] staging wave at the barrier, [21] tiles. */
 int xsd_debug_stamps(xsd_engine* e, int enable, unsigned long long* out32);
 /* Diagnostic only (pure host arithmetic, no device needed): the number of workgroups a persistent split-mode conv launch over `ntiles`
- * tiles uses on a device of `ncu` compute units (csrc/xsd_kernels.h: persistent_grid -- the full grid, or the balanced one when the
- * launch has at most 8 rounds and its last round would fill at most 0.35 of the CUs). */
+ * tiles uses on a device of `ncu` compute units (csrc/xsd_kernels.h: persistent_grid -- `ntiles` when ntiles <= ncu; with
+ * rounds = ceil(ntiles / ncu), the balanced grid ceil(ntiles / rounds) when rounds <= 8; otherwise the full grid, `ncu`). */
 int xsd_debug_persistent_grid(int ntiles, int ncu);
 /* Diagnostic only: hipOccupancyMaxActiveBlocksPerMultiprocessor of the split forward conv kernel at a dynamic LDS size. */
 int xsd_debug_occupancy(int lds_bytes);

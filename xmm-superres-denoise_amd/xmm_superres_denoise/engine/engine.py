@@ -248,9 +248,14 @@ class _ForwardEngine:
         if x.dim() != 4 or x.shape[1] != self._cin:
             raise XsdError(f"x must be [B,{self._cin},H,W] (got {tuple(x.shape)})")
         B, _, H, W = x.shape
-        y = torch.empty((B, self._cout, H * self._scale, W * self._scale), device=x.device, dtype=torch.float32)
+        Ho, Wo = self.out_size(H, W)
+        y = torch.empty((B, self._cout, Ho, Wo), device=x.device, dtype=torch.float32)
         check(self._c("forward")(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
         return y
+
+    def out_size(self, H: int, W: int) -> tuple[int, int]:
+        """(Ho, Wo) of forward's output for an H x W input"""
+        return H * self._scale, W * self._scale
 
     # ---- math mode of the GEMMs (include/xsd.h: xsd_swinfir_set_math / xsd_hat_set_math); the mode numbers of Engine.MATH
     MATH = {"fp32": 0, "bf16x6": 3}
@@ -297,31 +302,44 @@ class RestormerEngine(_ForwardEngine):
         self.in_channels, self.out_channels = int(inp_channels), int(out_channels)
 
 
-class SwinFIREngine(_ForwardEngine):
-    """One SwinFIR engine per module per GPU (xsd_swinfir_create / _destroy): forward only."""
+class _SwinEngine(_ForwardEngine):
+    """What the SwinFIR, HAT and SwinIR engines share: the 17 configuration fields their C structs have in common.  A subclass names its
+    struct (CONFIG), its resi_connection forms (RESI; an unknown one gets the index behind the last, which create refuses) and, in
+    `extra`, the fields of its own."""
 
     UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
-    RESI = ("SFB", "1conv", "HSFB", "identity")
-    PREFIX = "xsd_swinfir_"
-    NAME = "SwinFIR"
+    CONFIG = None
+    RESI = ()
+
+    def _upsampler_index(self, upsampler: str) -> int:
+        return self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3
 
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
                  qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
-                 resi_connection: str):
+                 resi_connection: str, **extra):
         super().__init__()
         depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
         if len(depths) > 16 or len(num_heads) < len(depths):
-            raise XsdError(f"SwinFIR: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
-        cfg = _lib.XsdSwinFIRConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
-                                    in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
-                                    depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
-                                    window_size=int(window_size), qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)),
-                                    patch_norm=int(bool(patch_norm)), upscale=int(upscale),
-                                    upsampler=self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3,
-                                    resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 3,
-                                    mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range))
+            raise XsdError(f"{self.NAME}: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
+        cfg = self.CONFIG(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
+                          in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
+                          depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
+                          window_size=int(window_size), qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)),
+                          patch_norm=int(bool(patch_norm)), upscale=int(upscale),
+                          upsampler=self._upsampler_index(upsampler),
+                          resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else len(self.RESI),
+                          mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range), **extra)
         self._create(cfg, in_chans, in_chans, upscale)
         self.in_chans, self.upscale = int(in_chans), int(upscale)
+
+
+class SwinFIREngine(_SwinEngine):
+    """One SwinFIR engine per module per GPU (xsd_swinfir_create / _destroy): forward only."""
+
+    CONFIG = _lib.XsdSwinFIRConfig
+    RESI = ("SFB", "1conv", "HSFB", "identity")
+    PREFIX = "xsd_swinfir_"
+    NAME = "SwinFIR"
 
     @_on_engine_device
     def fourier_pair(self, x: torch.Tensor, spec: torch.Tensor | None = None) -> torch.Tensor:
@@ -340,10 +358,10 @@ class SwinFIREngine(_ForwardEngine):
         return x
 
 
-class HATEngine(_ForwardEngine):
+class HATEngine(_SwinEngine):
     """One HAT engine per module per GPU (xsd_hat_create / _destroy): forward only."""
 
-    UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
+    CONFIG = _lib.XsdHATConfig
     RESI = ("1conv", "identity")
     PREFIX = "xsd_hat_"
     NAME = "HAT"
@@ -351,50 +369,24 @@ class HATEngine(_ForwardEngine):
     def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, compress_ratio: int,
                  squeeze_factor: int, conv_scale: float, overlap_ratio: float, mlp_ratio: float, qkv_bias: bool, qk_scale, ape: bool,
                  patch_norm: bool, upscale: int, img_range: float, upsampler: str, resi_connection: str):
-        super().__init__()
-        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
-        if len(depths) > 16 or len(num_heads) < len(depths):
-            raise XsdError(f"HAT: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
-        cfg = _lib.XsdHATConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
-                                in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
-                                depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
-                                window_size=int(window_size), compress_ratio=int(compress_ratio), squeeze_factor=int(squeeze_factor),
-                                qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)), patch_norm=int(bool(patch_norm)), upscale=int(upscale),
-                                upsampler=self.UPSAMPLERS.index(upsampler) if upsampler in self.UPSAMPLERS else 3,
-                                resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 2,
-                                mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range),
-                                conv_scale=float(conv_scale), overlap_ratio=float(overlap_ratio))
-        self._create(cfg, in_chans, in_chans, upscale)
-        self.in_chans, self.upscale = int(in_chans), int(upscale)
+        super().__init__(img_size, patch_size, in_chans, embed_dim, depths, num_heads, window_size, mlp_ratio, qkv_bias, qk_scale, ape,
+                         patch_norm, upscale, img_range, upsampler, resi_connection, compress_ratio=int(compress_ratio),
+                         squeeze_factor=int(squeeze_factor), conv_scale=float(conv_scale), overlap_ratio=float(overlap_ratio))
 
 
-class SwinIREngine(_ForwardEngine):
+class SwinIREngine(_SwinEngine):
     """One SwinIR engine per module per GPU (xsd_swinir_create / _destroy): forward only, any image size (the engine reflect-pads to
     multiples of window_size and crops back)."""
 
-    UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect", "nearest+conv", "")
+    CONFIG = _lib.XsdSwinIRConfig
     RESI = ("1conv", "3conv")
     PREFIX = "xsd_swinir_"
     NAME = "SwinIR"
 
-    def __init__(self, img_size, patch_size, in_chans: int, embed_dim: int, depths, num_heads, window_size: int, mlp_ratio: float,
-                 qkv_bias: bool, qk_scale, ape: bool, patch_norm: bool, upscale: int, img_range: float, upsampler: str,
-                 resi_connection: str):
-        super().__init__()
-        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
-        if len(depths) > 16 or len(num_heads) < len(depths):
-            raise XsdError(f"SwinIR: at most 16 layers with one num_heads entry each (got depths {depths}, num_heads {num_heads})")
-        if upsampler not in self.UPSAMPLERS:
+    def _upsampler_index(self, upsampler: str) -> int:
+        if upsampler not in self.UPSAMPLERS:       # "" is a head of SwinIR's: an unknown name must not become it
             raise XsdError(f"SwinIR: unknown upsampler {upsampler!r}: {self.UPSAMPLERS}")
-        cfg = _lib.XsdSwinIRConfig(img_size=(ctypes.c_int32 * 2)(*img_size), patch_size=(ctypes.c_int32 * 2)(*patch_size),
-                                   in_chans=int(in_chans), embed_dim=int(embed_dim), num_layers=len(depths),
-                                   depths=(ctypes.c_int32 * 16)(*depths), num_heads=(ctypes.c_int32 * 16)(*num_heads[:len(depths)]),
-                                   window_size=int(window_size), qkv_bias=int(bool(qkv_bias)), ape=int(bool(ape)),
-                                   patch_norm=int(bool(patch_norm)), upscale=int(upscale), upsampler=self.UPSAMPLERS.index(upsampler),
-                                   resi_connection=self.RESI.index(resi_connection) if resi_connection in self.RESI else 2,
-                                   mlp_ratio=float(mlp_ratio), qk_scale=float(qk_scale or 0.0), img_range=float(img_range))
-        self._create(cfg, in_chans, in_chans, upscale)
-        self.in_chans, self.upscale = int(in_chans), int(upscale)
+        return self.UPSAMPLERS.index(upsampler)
 
     def out_size(self, H: int, W: int) -> tuple[int, int]:
         """(Ho, Wo) of forward's output for an H x W input (xsd_swinir_out_size): H upscale x W upscale for every head that enlarges;
@@ -402,17 +394,6 @@ class SwinIREngine(_ForwardEngine):
         ho, wo = ctypes.c_int(), ctypes.c_int()
         check(self.L.xsd_swinir_out_size(self.h, int(H), int(W), ctypes.byref(ho), ctypes.byref(wo)))
         return ho.value, wo.value
-
-    @_on_engine_device
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        _require_cuda_f32(x, "x")
-        if x.dim() != 4 or x.shape[1] != self._cin:
-            raise XsdError(f"x must be [B,{self._cin},H,W] (got {tuple(x.shape)})")
-        B, _, H, W = x.shape
-        Ho, Wo = self.out_size(H, W)
-        y = torch.empty((B, self._cout, Ho, Wo), device=x.device, dtype=torch.float32)
-        check(self.L.xsd_swinir_forward(self.h, x.data_ptr(), y.data_ptr(), B, H, W, _stream_ptr(x.device)))
-        return y
 
 
 @_on_tensor_device

@@ -146,15 +146,12 @@ def load_model(checkpoint: str, name: str = "rrdb_denoise", lr_res: int = 416, d
     from xmm_superres_denoise.config.config import model_cfg
     from xmm_superres_denoise.models import Model
     from xmm_superres_denoise.train import load_checkpoint
-    if name == "restormer" and math not in (None, "fp32"):
-        raise ValueError(f"restormer: math mode {math!r} is not supported: the Restormer engine computes in 'fp32' only")
     hr_res = lr_res * (2 if name in ("esr_gen", "swinfir", "hat") else 1)      # SwinFIR, HAT: upscale 2, the class default the factory keeps
     model = Model(model_cfg(name) if dim is None else model_cfg(name, dim=int(dim)), (lr_res, lr_res), (hr_res, hr_res))
-    if name == "hat":
-        model.configure_model(forward_only_hat=True)      # forward only; a bare configure_model refuses HAT (models/model.py)
+    model.configure_model(forward_only_hat=name == "hat")     # forward only; a bare configure_model refuses HAT (models/model.py)
+    if math is not None:
+        model.model.set_math(math)      # a mode the network does not take is refused before the checkpoint is read
     load_checkpoint(checkpoint, model)
-    if math is not None and name != "restormer":
-        model.model.set_math(math)
     return model.to(device)
 
 

@@ -1,21 +1,117 @@
-"""The flat parameter buffer the engines read (include/xsd.h: "flat params"), shared by the generator modules: every parameter a
-view into one contiguous fp32 buffer in state_dict order, the version counter that says when it changed, and the copy / pickle
-rule for the engine handle."""
+"""What the engine-backed modules share (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, HAT, SwinIR): the flat parameter buffer the engines
+read (include/xsd.h: "flat params": every parameter a view into one contiguous fp32 buffer in state_dict order) with the version
+counter that says when it changed, the engine handle and its re-pack rule, the math mode, the copy / pickle rule, the input checks and
+the one forward-only autograd function.  A module provides _make_engine, its constructor checks and its forward's size rule."""
 from __future__ import annotations
 
 import torch
+from torch.autograd.function import once_differentiable
+
+from xmm_superres_denoise.engine import XsdError
+
+
+class _ForwardOnlyFn(torch.autograd.Function):
+    """The forward of a module without a backward on the engine: works in any grad mode; a backward that reaches it is refused by name."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        ctx.network = module.NETWORK
+        eng = module._get_engine(x.device)
+        module._pack_if_changed()
+        return eng.forward(x.contiguous())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        raise RuntimeError(f"{ctx.network} training is not on the MI355X engine: its backward is not implemented (forward only: "
+                           "inference, infer.py, validation / test metrics)")
 
 
 class FlatParams:
-    """Mixin for an nn.Module with the attributes _engine, _engine_dev, _flat and _plist."""
+    """Base of an nn.Module that computes through an engine.  A subclass names its engine class (ENGINE: its MATH table lists the math
+    modes) and its network (NETWORK), calls _init_engine_state() at the end of __init__ and provides _make_engine()."""
+
+    ENGINE = None
+    NETWORK = ""
+    DEFAULT_MATH = "fp32"       # what get_math answers before set_math; None: the engine's own default, known once an engine exists
+
+    def _init_engine_state(self):
+        self._engine = None
+        self._engine_dev = None
+        self._flat = None
+        self._plist = None
+        self._packed_key = None
+        self._math = None       # None: the engine's default
 
     # ---- copies and pickles (copy.deepcopy for EMA / SWA copies, torch.save(module), spawn-style launchers) --------------------
     def __getstate__(self):
         """The engine handle belongs to this process and this module: a copy or an unpickled module builds its own (and lays its own
-        flat parameter buffer) at its first forward, exactly like a freshly constructed one."""
+        flat parameter buffer, and packs) at its first forward, exactly like a freshly constructed one.  The math mode is carried."""
         st = self.__dict__.copy()
-        st["_engine"] = st["_engine_dev"] = st["_flat"] = st["_plist"] = None
+        st["_engine"] = st["_engine_dev"] = st["_flat"] = st["_plist"] = st["_packed_key"] = None
         return st
+
+    # ---- math mode -----------------------------------------------------------------------------------------------------------------
+    def _math_refusal(self, mode: str) -> Exception:
+        return ValueError(f"{self.NETWORK}: math mode {mode!r} is not supported; the modes are {sorted(self.ENGINE.MATH)}"
+                          + (" (the fp16 terms of 'f16x3' need a per-tensor scale that these kernels do not publish)" if mode == "f16x3" else ""))
+
+    def set_math(self, mode: str):
+        """Math mode of the engine's matrix kernels (ENGINE.set_math; ENGINE.MATH lists the modes).  Kept until an engine exists, applied
+        again to the engine a device move creates, and carried by copies and pickles."""
+        if mode not in self.ENGINE.MATH:
+            raise self._math_refusal(mode)
+        self._math = mode
+        if self._engine is not None:
+            self._engine.set_math(mode)
+        return self
+
+    def get_math(self) -> str:
+        return getattr(self, "_math", None) or self.DEFAULT_MATH
+
+    # ---- engine --------------------------------------------------------------------------------------------------------------------
+    def _make_engine(self):
+        """the one ENGINE(...) call, from the module's constructor arguments"""
+        raise NotImplementedError
+
+    def _get_engine(self, device):
+        if not torch.device(device).type == "cuda":
+            raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
+        flat = self.flatten_parameters()
+        if flat.device != torch.device(device):
+            raise XsdError(f"module parameters are on {flat.device} but the input is on {device}")
+        if self._engine is None or self._engine_dev != flat.device:
+            with torch.cuda.device(flat.device):
+                self._engine = self._make_engine()
+            self._engine_dev = flat.device
+            self._packed_key = None
+            if getattr(self, "_math", None) is not None:
+                self._engine.set_math(self._math)
+        return self._engine
+
+    def _pack_if_changed(self):
+        """Re-pack after any parameter update torch knows of (optimizer step, load_state_dict, in-place edits: the version counters
+        of the parameters and of the flat buffer) or a new flat buffer."""
+        key = (self._flat.data_ptr(), self._param_version())
+        if key != self._packed_key:
+            self._engine.pack(self._flat)
+            self._packed_key = key
+
+    # ---- forward -------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_input(x: torch.Tensor, channels: int | None):
+        """`channels`: None leaves the shape to the engine"""
+        if x.dtype != torch.float32:
+            raise XsdError(f"input must be float32 (got {x.dtype})")
+        if channels is not None and (x.dim() != 4 or x.shape[1] != channels):
+            raise XsdError(f"input must be [B,{channels},H,W] (got {tuple(x.shape)})")
+
+    def _forward_only(self, x: torch.Tensor, channels: int, Ho: int, Wo: int):
+        """x through the engine's forward -> [B, channels, Ho, Wo]"""
+        self._get_engine(x.device)
+        if x.shape[0] == 0:      # an empty batch answers like torch's convs: empty output, no launch
+            return x.new_empty((0, channels, Ho, Wo))
+        return _ForwardOnlyFn.apply(self, x, *self._plist)
 
     # ---- flat parameter buffer ---------------------------------------------------------------------------------
     def flatten_parameters(self):

@@ -133,6 +133,8 @@ class _EngineFn(torch.autograd.Function):
 
 class _GeneratorRRDB(FlatParams, nn.Module):
     _kind = None
+    ENGINE = Engine
+    DEFAULT_MATH = None     # the engine's own: env XSD_MATH, else f16x3 (Engine.get_math says which)
 
     def __init__(self, in_channels: int, out_channels: int, num_filters: int, num_res_blocks: int,
                  memory_efficient: bool = False):
@@ -165,42 +167,20 @@ class _GeneratorRRDB(FlatParams, nn.Module):
         self.conv_last.weight.data.uniform_(-stdv, stdv + positive_offset_std * stdv)
         if self.conv_last.bias is not None:
             self.conv_last.bias.data.uniform_(-stdv, stdv + positive_offset_std * stdv)
-        self._engine = None
-        self._engine_dev = None
-        self._flat = None
-        self._plist = None
-        self._math = None  # None: engine default (env XSD_MATH, else f16x3)
+        self._init_engine_state()
 
     def _num_upsample(self):
         return 1
 
-    def set_math(self, mode: str):
-        """Math mode of the conv kernels (Engine.set_math): 'fp32' (exact), 'bf16x6' (strict split), 'f16x3' (default split)."""
-        if mode not in Engine.MATH:
-            raise ValueError(mode)
-        self._math = mode
-        if self._engine is not None:
-            self._engine.set_math(mode)
-        return self
+    def _math_refusal(self, mode: str) -> Exception:
+        return ValueError(mode)
 
-    def _get_engine(self, device):
-        if not torch.device(device).type == "cuda":
-            raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
-        flat = self.flatten_parameters()
-        if flat.device != torch.device(device):
-            raise XsdError(f"module parameters are on {flat.device} but the input is on {device}")
-        if self._engine is None or self._engine_dev != flat.device:
-            with torch.cuda.device(flat.device):
-                self._engine = Engine(self._kind, self.in_channels, self.out_channels, self.num_filters,
-                                      self.num_res_blocks, self._num_upsample(), self.memory_efficient)
-            self._engine_dev = flat.device
-            if self._math is not None:
-                self._engine.set_math(self._math)
-        return self._engine
+    def _make_engine(self):
+        return Engine(self._kind, self.in_channels, self.out_channels, self.num_filters, self.num_res_blocks, self._num_upsample(),
+                      self.memory_efficient)
 
     def forward(self, x):
-        if x.dtype != torch.float32:
-            raise XsdError(f"input must be float32 (got {x.dtype})")
+        self._check_input(x, None)      # the shape is the engine's to check
         self._get_engine(x.device)
         # grad mode is off inside autograd.Function.forward, so decide here whether activations must be kept
         need = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self._plist))

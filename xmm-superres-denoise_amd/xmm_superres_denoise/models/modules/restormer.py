@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import torch
 from torch import nn
-from torch.autograd.function import once_differentiable
 
 from xmm_superres_denoise.engine import RestormerEngine, XsdError
 
@@ -78,21 +77,10 @@ class _Upsample(nn.Module):             # reference :202-213
         self.body = nn.Sequential(nn.Conv2d(n_feat, n_feat * 2, kernel_size=3, stride=1, padding=1, bias=False), nn.PixelShuffle(2))
 
 
-class _RestormerFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, module, x, *params):
-        eng = module._get_engine(x.device)
-        module._pack_if_changed()
-        return eng.forward(x.contiguous())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        raise RuntimeError("Restormer training is not on the MI355X engine: its backward is not implemented (forward only: "
-                           "inference, infer.py, validation / test metrics)")
-
-
 class Restormer(FlatParams, nn.Module):
+    ENGINE = RestormerEngine
+    NETWORK = "Restormer"
+
     def __init__(self, inp_channels=3, out_channels=3, dim=48, num_blocks=(4, 6, 6, 8), num_refinement_blocks=4, heads=(1, 2, 4, 8),
                  ffn_expansion_factor=2.66, bias=False, LayerNorm_type="WithBias", dual_pixel_task=False):
         super().__init__()
@@ -147,49 +135,19 @@ class Restormer(FlatParams, nn.Module):
         self.refinement = level(num_refinement_blocks, dim * 2, heads[0])
         self.dual_pixel_task = False
         self.output = nn.Conv2d(dim * 2, out_channels, kernel_size=3, stride=1, padding=1, bias=bias)
-        self._engine = None
-        self._engine_dev = None
-        self._flat = None
-        self._plist = None
-        self._packed_key = None
+        self._init_engine_state()
 
-    def __getstate__(self):
-        st = super().__getstate__()
-        st["_packed_key"] = None
-        return st
+    def _math_refusal(self, mode: str) -> Exception:
+        return ValueError(f"restormer: math mode {mode!r} is not supported: the Restormer engine computes in 'fp32' only")
 
-    def _get_engine(self, device):
-        if not torch.device(device).type == "cuda":
-            raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
-        flat = self.flatten_parameters()
-        if flat.device != torch.device(device):
-            raise XsdError(f"module parameters are on {flat.device} but the input is on {device}")
-        if self._engine is None or self._engine_dev != flat.device:
-            with torch.cuda.device(flat.device):
-                self._engine = RestormerEngine(self.inp_channels, self.out_channels, self.dim, self.num_blocks, self.num_refinement_blocks,
-                                               self.heads, self.ffn_expansion_factor, self.bias, self.LayerNorm_type == "BiasFree")
-            self._engine_dev = flat.device
-            self._packed_key = None
-        return self._engine
-
-    def _pack_if_changed(self):
-        """Re-pack after any parameter update torch knows of (optimizer step, load_state_dict, in-place edits: the version counters
-        of the parameters and of the flat buffer, as the RRDB recompute guard watches them) or a new flat buffer."""
-        key = (self._flat.data_ptr(), self._param_version())
-        if key != self._packed_key:
-            self._engine.pack(self._flat)
-            self._packed_key = key
+    def _make_engine(self):
+        return RestormerEngine(self.inp_channels, self.out_channels, self.dim, self.num_blocks, self.num_refinement_blocks, self.heads,
+                               self.ffn_expansion_factor, self.bias, self.LayerNorm_type == "BiasFree")
 
     def forward(self, inp_img):
         x = inp_img
-        if x.dtype != torch.float32:
-            raise XsdError(f"input must be float32 (got {x.dtype})")
-        if x.dim() != 4 or x.shape[1] != self.inp_channels:
-            raise XsdError(f"input must be [B,{self.inp_channels},H,W] (got {tuple(x.shape)})")
+        self._check_input(x, self.inp_channels)
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise XsdError(f"Restormer needs H and W divisible by 8 (three PixelUnshuffle(2) levels, restormer.py:188-199); "
                            f"got {x.shape[2]} x {x.shape[3]}")
-        self._get_engine(x.device)
-        if x.shape[0] == 0:      # an empty batch answers like torch's convs: empty output, no launch
-            return x.new_empty((0, self.out_channels, x.shape[2], x.shape[3]))
-        return _RestormerFn.apply(self, x, *self._plist)
+        return self._forward_only(x, self.out_channels, x.shape[2], x.shape[3])

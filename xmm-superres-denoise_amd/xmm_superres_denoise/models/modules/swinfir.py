@@ -10,94 +10,11 @@ buffers in the reference's layout; the computation is the engine's.
 """
 from __future__ import annotations
 
-import math
-
-import torch
 from torch import nn
-from torch.autograd.function import once_differentiable
 
 from xmm_superres_denoise.engine import SwinFIREngine, XsdError, fft_size_supported
 
-from .flat_params import FlatParams
-
-MAX_WINDOW = 16          # csrc/swinfir.hip: sw_attn_kernel takes at most 8 tiles of 32 tokens per window
-MAX_HEAD_DIM = 32        # one 32-column MFMA tile per head
-
-
-def _2tuple(v):
-    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-
-
-def _init_weights(m):
-    # reference tools.py init_weights, applied by SwinFIR.__init__ to every submodule; timm's trunc_normal_ is the same truncated
-    # normal draw as torch.nn.init.trunc_normal_ (bounds +-2, std 0.02)
-    if isinstance(m, nn.Linear):
-        nn.init.trunc_normal_(m.weight, std=0.02)
-        if m.bias is not None:
-            nn.init.constant_(m.bias, 0)
-    elif isinstance(m, nn.LayerNorm):
-        nn.init.constant_(m.bias, 0)
-        nn.init.constant_(m.weight, 1.0)
-
-
-def relative_position_index(ws: int) -> torch.Tensor:
-    """[ws^2, ws^2] index into the (2 ws - 1)^2 bias table: (dy + ws - 1) (2 ws - 1) + (dx + ws - 1) for tokens i, j"""
-    c = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
-    rel = (c[:, :, None] - c[:, None, :]).permute(1, 2, 0).contiguous() + (ws - 1)
-    return rel[:, :, 0] * (2 * ws - 1) + rel[:, :, 1]
-
-
-def shift_mask(h: int, w: int, ws: int, shift: int) -> torch.Tensor:
-    """[nW, ws^2, ws^2]: 0 between tokens of the same region of the rolled image, -100 otherwise (the reference's attn_mask)"""
-    def region(n):
-        r = torch.zeros(n)
-        r[n - ws:n - shift] = 1
-        r[n - shift:] = 2
-        return r
-    ids = (3 * region(h)[:, None] + region(w)[None, :])
-    win = ids.view(h // ws, ws, w // ws, ws).permute(0, 2, 1, 3).reshape(-1, ws * ws)
-    d = win[:, None, :] - win[:, :, None]
-    return torch.where(d != 0, torch.tensor(-100.0), torch.tensor(0.0))
-
-
-class _Mlp(nn.Module):                 # modules.py Mlp
-    def __init__(self, dim: int, hidden: int):
-        super().__init__()
-        self.fc1 = nn.Linear(dim, hidden)
-        self.act = nn.GELU()
-        self.fc2 = nn.Linear(hidden, dim)
-
-
-class _WindowAttention(nn.Module):     # modules.py WindowAttention: table, index buffer, qkv, proj; the table drawn last
-    def __init__(self, dim: int, ws: int, num_heads: int, qkv_bias: bool):
-        super().__init__()
-        self.num_heads = num_heads
-        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * ws - 1) * (2 * ws - 1), num_heads))
-        self.register_buffer("relative_position_index", relative_position_index(ws))
-        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
-        self.proj = nn.Linear(dim, dim)
-        nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
-
-
-class _SwinBlock(nn.Module):           # modules.py SwinTransformerBlock
-    def __init__(self, dim, input_resolution, num_heads, window_size, shift_size, mlp_ratio, qkv_bias):
-        super().__init__()
-        self.window_size, self.shift_size = window_size, shift_size
-        if min(input_resolution) <= window_size:
-            self.shift_size, self.window_size = 0, min(input_resolution)
-        self.norm1 = nn.LayerNorm(dim)
-        self.attn = _WindowAttention(dim, self.window_size, num_heads, qkv_bias)
-        self.norm2 = nn.LayerNorm(dim)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
-        mask = shift_mask(input_resolution[0], input_resolution[1], self.window_size, self.shift_size) if self.shift_size > 0 else None
-        self.register_buffer("attn_mask", mask)
-
-
-class _BasicLayer(nn.Module):
-    def __init__(self, dim, input_resolution, depth, num_heads, window_size, mlp_ratio, qkv_bias):
-        super().__init__()
-        self.blocks = nn.ModuleList([_SwinBlock(dim, input_resolution, num_heads, window_size, 0 if i % 2 == 0 else window_size // 2,
-                                                mlp_ratio, qkv_bias) for i in range(depth)])
+from .swin_common import SwinFamily, _BasicLayer, _init_weights, _PatchEmbed
 
 
 class _ResB(nn.Module):                # swinfir.py ResB
@@ -136,151 +53,47 @@ class _RSTB(nn.Module):                # swinfir.py RSTB (its patch_embed / patc
         self.conv = _SFB(dim) if resi_connection == "SFB" else nn.Conv2d(dim, dim, 3, 1, 1)
 
 
-class _PatchEmbed(nn.Module):
-    def __init__(self, dim: int, patch_norm: bool):
-        super().__init__()
-        self.norm = nn.LayerNorm(dim) if patch_norm else None
+class SwinFIR(SwinFamily):
+    ENGINE = SwinFIREngine
+    NETWORK = "SwinFIR"
+    RGB_MEAN = (0.3014, 0.3152, 0.3094)
 
-
-class _SwinFIRFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, module, x, *params):
-        eng = module._get_engine(x.device)
-        module._pack_if_changed()
-        return eng.forward(x.contiguous())
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        raise RuntimeError("SwinFIR training is not on the MI355X engine: its backward is not implemented (forward only: "
-                           "inference, infer.py, validation / test metrics)")
-
-
-class SwinFIR(FlatParams, nn.Module):
     def __init__(self, img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths=(6, 6, 6, 6), num_heads=(6, 6, 6, 6), window_size=7,
                  mlp_ratio=4.0, qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.1,
                  norm_layer=nn.LayerNorm, ape=False, patch_norm=True, use_checkpoint=False, upscale=2, img_range=1.0, upsampler="",
                  resi_connection="SFB"):
         super().__init__()
         # What the engine cannot compute is said HERE, not at the first forward.
-        if ape:
-            raise ValueError("SwinFIR: ape=True (absolute position embedding) is not supported by the MI355X engine")
         if upsampler != "pixelshuffle":
             raise ValueError(f"SwinFIR: upsampler {upsampler!r} is not supported by the MI355X engine (only \"pixelshuffle\", the XMM "
                              "configuration's)")
         if resi_connection not in ("SFB", "1conv"):
             raise ValueError(f"SwinFIR: resi_connection {resi_connection!r} is not supported by the MI355X engine (only \"SFB\" and "
                              "\"1conv\")")
-        if norm_layer is not nn.LayerNorm:
-            raise ValueError("SwinFIR: only norm_layer=nn.LayerNorm is supported by the MI355X engine")
         if upscale not in (2, 3, 4, 8):
             raise ValueError(f"SwinFIR: scale {upscale} is not supported. Supported scales: 2^n and 3 (up to 8 here).")
-        if not 1 <= int(in_chans) <= 64 or not 2 <= int(embed_dim) <= 4096:
-            raise ValueError(f"SwinFIR: in_chans must be in [1, 64] and embed_dim in [2, 4096] (got {in_chans}, {embed_dim})")
-        depths, num_heads = [int(d) for d in depths], [int(h) for h in num_heads]
-        if len(depths) > 16 or len(num_heads) < len(depths) or any(not 0 <= d <= 64 for d in depths):
-            raise ValueError(f"SwinFIR: at most 16 layers of 0..64 blocks, one num_heads entry each (got {depths}, {num_heads})")
-        for i, h in enumerate(num_heads[:len(depths)]):
-            if h < 1 or embed_dim % h or embed_dim // h > MAX_HEAD_DIM:
-                raise ValueError(f"SwinFIR: num_heads[{i}] = {h} must divide embed_dim {embed_dim} into at most {MAX_HEAD_DIM} channels "
-                                 "per head")
-        if not mlp_ratio > 0 or int(embed_dim * mlp_ratio) < 1:
-            raise ValueError(f"SwinFIR: mlp_ratio {mlp_ratio} gives no hidden width")
-        if not img_range > 0:
-            raise ValueError("SwinFIR: img_range must be positive")
-        if qk_scale is not None and not qk_scale >= 0:
-            # the reference would use a negative scale as given; the engine takes None / 0 (head_dim^-0.5) or a positive one
-            raise ValueError(f"SwinFIR: qk_scale {qk_scale} is not supported by the MI355X engine (None, or a positive scale)")
-        img2, patch2 = _2tuple(img_size), _2tuple(patch_size)
-        res = [img2[0] // patch2[0], img2[1] // patch2[1]]
-        self.window = min(res) if min(res) <= window_size else window_size     # the effective window (modules.py:236-239)
-        if not 1 <= self.window <= MAX_WINDOW:
-            raise ValueError(f"SwinFIR: an effective window of {self.window} is not supported (1..{MAX_WINDOW}: at most 256 tokens)")
-        self.img_size, self.patch_size, self.in_chans, self.embed_dim = img2, patch2, int(in_chans), int(embed_dim)
-        self.depths, self.num_heads, self.window_size, self.mlp_ratio = depths, num_heads, int(window_size), float(mlp_ratio)
-        self.qkv_bias, self.qk_scale, self.ape, self.patch_norm = bool(qkv_bias), qk_scale, False, bool(patch_norm)
-        self.upscale, self.img_range, self.upsampler, self.resi_connection = int(upscale), float(img_range), upsampler, resi_connection
-        self.num_layers, self.num_features, self.patches_resolution = len(depths), int(embed_dim), res
-        # the eval forward ignores these; TrainableSwinFIR (swinfir_train.py) reads them
-        self.drop_rate, self.attn_drop_rate, self.drop_path_rate = float(drop_rate), float(attn_drop_rate), float(drop_path_rate)
-        if in_chans == 3:
-            self.mean = torch.Tensor((0.3014, 0.3152, 0.3094)).view(1, 3, 1, 1)
-        else:
-            self.mean = torch.zeros(1, 1, 1, 1)
-        num_feat = 64
+        res = self._swin_args(img_size, patch_size, in_chans, embed_dim, depths, num_heads, window_size, mlp_ratio, qkv_bias, qk_scale,
+                              drop_rate, attn_drop_rate, drop_path_rate, norm_layer, ape, patch_norm, upscale, img_range, upsampler,
+                              resi_connection)
+        self._effective_window(res, window_size)
         # same construction order as the reference (:315-401) => same parameter order and the same default init under one torch seed
         self.conv_first = nn.Conv2d(in_chans, embed_dim, 3, 1, 1)
         self.patch_embed = _PatchEmbed(embed_dim, patch_norm)
-        self.layers = nn.ModuleList([_RSTB(embed_dim, res, depths[i], num_heads[i], window_size, mlp_ratio, qkv_bias, resi_connection)
-                                     for i in range(len(depths))])
+        self.layers = nn.ModuleList([_RSTB(embed_dim, res, self.depths[i], self.num_heads[i], window_size, mlp_ratio, qkv_bias,
+                                           resi_connection) for i in range(len(self.depths))])
         self.norm = nn.LayerNorm(embed_dim)
         self.conv_after_body = nn.Conv2d(embed_dim, embed_dim, 3, 1, 1)
-        self.conv_before_upsample = nn.Sequential(nn.Conv2d(embed_dim, num_feat, 3, 1, 1), nn.LeakyReLU(inplace=True))
-        ups = []
-        if upscale == 3:
-            ups += [nn.Conv2d(num_feat, 9 * num_feat, 3, 1, 1), nn.PixelShuffle(3)]
-        else:
-            for _ in range(int(math.log(upscale, 2))):
-                ups += [nn.Conv2d(num_feat, 4 * num_feat, 3, 1, 1), nn.PixelShuffle(2)]
-        self.upsample = nn.Sequential(*ups)
-        self.conv_last = nn.Conv2d(num_feat, in_chans, 3, 1, 1)
+        self._pixelshuffle_head(embed_dim, in_chans, upscale)
         self.apply(_init_weights)
-        self._engine = None
-        self._engine_dev = None
-        self._flat = None
-        self._plist = None
-        self._packed_key = None
-        self._math = None  # None: the engine's default (fp32)
+        self._init_engine_state()
 
-    def set_math(self, mode: str):
-        """Math mode of the linear layers and 3x3 convs (SwinFIREngine.set_math): 'fp32' (exact, the default) or 'bf16x6' (strict split).  Kept
-        until an engine exists, applied again to the engine a device move creates, and carried by copies and pickles."""
-        if mode not in SwinFIREngine.MATH:
-            raise ValueError(f"SwinFIR: math mode {mode!r} is not supported; the modes are {sorted(SwinFIREngine.MATH)}"
-                             + (" (the fp16 terms of 'f16x3' need a per-tensor scale that these kernels do not publish)" if mode == "f16x3" else ""))
-        self._math = mode
-        if self._engine is not None:
-            self._engine.set_math(mode)
-        return self
-
-    def get_math(self) -> str:
-        return getattr(self, "_math", None) or "fp32"
-
-    def __getstate__(self):
-        st = super().__getstate__()
-        st["_packed_key"] = None
-        return st
-
-    def _get_engine(self, device):
-        if not torch.device(device).type == "cuda":
-            raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
-        flat = self.flatten_parameters()
-        if flat.device != torch.device(device):
-            raise XsdError(f"module parameters are on {flat.device} but the input is on {device}")
-        if self._engine is None or self._engine_dev != flat.device:
-            with torch.cuda.device(flat.device):
-                self._engine = SwinFIREngine(self.img_size, self.patch_size, self.in_chans, self.embed_dim, self.depths, self.num_heads,
-                                             self.window_size, self.mlp_ratio, self.qkv_bias, self.qk_scale, self.ape, self.patch_norm,
-                                             self.upscale, self.img_range, self.upsampler, self.resi_connection)
-            self._engine_dev = flat.device
-            self._packed_key = None
-            if getattr(self, "_math", None) is not None:
-                self._engine.set_math(self._math)
-        return self._engine
-
-    def _pack_if_changed(self):
-        """Re-pack after any parameter update torch knows of (optimizer step, load_state_dict, in-place edits: the version counters
-        of the parameters and of the flat buffer) or a new flat buffer."""
-        key = (self._flat.data_ptr(), self._param_version())
-        if key != self._packed_key:
-            self._engine.pack(self._flat)
-            self._packed_key = key
+    def _make_engine(self):
+        return SwinFIREngine(self.img_size, self.patch_size, self.in_chans, self.embed_dim, self.depths, self.num_heads, self.window_size,
+                             self.mlp_ratio, self.qkv_bias, self.qk_scale, self.ape, self.patch_norm, self.upscale, self.img_range,
+                             self.upsampler, self.resi_connection)
 
     def forward(self, x):
-        if x.dtype != torch.float32:
-            raise XsdError(f"input must be float32 (got {x.dtype})")
-        if x.dim() != 4 or x.shape[1] != self.in_chans:
-            raise XsdError(f"input must be [B,{self.in_chans},H,W] (got {tuple(x.shape)})")
+        self._check_input(x, self.in_chans)
         H, W = int(x.shape[2]), int(x.shape[3])
         if H % self.window or W % self.window:
             raise XsdError(f"SwinFIR needs H and W that are multiples of the window size {self.window} (window_partition, "
@@ -290,8 +103,4 @@ class SwinFIR(FlatParams, nn.Module):
                 if not fft_size_supported(n):
                     raise XsdError(f"SwinFIR: FFT size {n} is not supported (the FourierUnit needs H and W of at most 4096 whose prime "
                                    f"factors are all <= 13); got {H} x {W}")
-        self._get_engine(x.device)
-        s = self.upscale
-        if x.shape[0] == 0:      # an empty batch answers like torch's convs: empty output, no launch
-            return x.new_empty((0, self.in_chans, H * s, W * s))
-        return _SwinFIRFn.apply(self, x, *self._plist)
+        return self._forward_only(x, self.in_chans, H * self.upscale, W * self.upscale)

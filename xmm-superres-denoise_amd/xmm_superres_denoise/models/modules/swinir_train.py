@@ -85,11 +85,7 @@ class TrainableSwin(nn.Module):
         return t / keep * mask.view(B, 1, 1)
 
     def _check_input(self, x: torch.Tensor):
-        m = self.module
-        if x.dtype != torch.float32:
-            raise XsdError(f"input must be float32 (got {x.dtype})")
-        if x.dim() != 4 or x.shape[1] != m.in_chans:
-            raise XsdError(f"input must be [B,{m.in_chans},H,W] (got {tuple(x.shape)})")
+        self.module._check_input(x, self.module.in_chans)
         if not x.is_cuda:
             raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
 
