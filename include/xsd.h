@@ -697,6 +697,22 @@ int xsd_test_gop(int op, float* dev_d, long long dbs, const float* dev_s, long l
 int xsd_test_gpack(int n, const int* host_cout, const int* host_cin, const float* dev_params, float* dev_wt, long long wt_cap,
                    float* dev_wblk, long long wblk_cap, long long* host_off, long long* host_count, void* stream);
 
+/* The loss kernels below the whole terms (csrc/loss_kernels.hip; kernel-level tests; synchronous; no product path calls these).
+ * xsd_loss_test_scale: ONE SSIM scale through the two host functions the SSIM / MS-SSIM chain runs per scale.  Forward: minmax,
+ * minmax_final, ssim_kernel<false>, image_stat -> dev_stat [B][2] device DOUBLES (per-image mean ssim, mean contrast term).  With
+ * dev_dy (and then dev_gup [B][2] = d loss / d (ssim_b, cs_b)) also: ties, ssim_kernel<true>, scale_bwd_scalars, back_filter ->
+ * dev_dy [B][H][W] (added to when accumulate != 0), plus 0.25 * dev_coarse [B][H / 2][W / 2] (or NULL) spread over 2 x 2 pixels as
+ * the chain does with the pooled scale's gradient.  Of cfg only sigma, k1, k2 are read.  host_scal11: the scale's scalars after the
+ * last launch -- pmin, pmax, tmin, tmax, data_range, c1, c2, from_p (1: the range is the prediction's), nmax, nmin (tie counts of the
+ * prediction's extremes; 1 after a forward-only call), ddr (d loss / d data_range).  Refused with XSD_ERR_ARG: what xsd_loss_eval
+ * refuses for the ssim term, dy without gup or the reverse, a coarse gradient without dy. */
+int xsd_loss_test_scale(const xsd_loss_config* cfg, const float* dev_y, const float* dev_target, const float* dev_gup, const float* dev_coarse,
+                        float* dev_dy, int accumulate, double* dev_stat, float* host_scal11, int B, int H, int W, void* stream);
+/* pool2_kernel alone: po, to [B][H / 2][W / 2] = the 2 x 2 means of p, t [B][H][W] (an odd last row / column is dropped). */
+int xsd_loss_test_pool2(const float* dev_p, const float* dev_t, float* dev_po, float* dev_to, int B, int H, int W, void* stream);
+/* launch_clamp_bwd alone (csrc/aux_kernels.hip): dpre = (0 <= pre <= 1) ? dy : 0 over n elements. */
+int xsd_test_clamp_bwd(const float* dev_pre, const float* dev_dy, float* dev_dpre, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,12 +91,19 @@ def ssim_scale(p, t, sigma=2.5, k1=0.01, k2=0.05):
         d_vp = np.where(vp_raw > 0, dL, 0.0)
         d_mp = dA * 2 * mt + dB * 2 * mp - d_cov * mt - d_vp * 2 * mp
         dp = _filt_full_T(d_mp, g) + 2 * p * _filt_full_T(d_vp, g) + t * _filt_full_T(d_cov, g)
+        hi, lo = p == p.max(), p == p.min()
+        info.update(d_dr=0.0, nmax=int(hi.sum()), nmin=int(lo.sum()))
         if from_p:
             d_dr = 2 * k1 * k1 * dr * (dA + dB).sum() + 2 * k2 * k2 * dr * (dU + dL).sum()
-            hi, lo = p == p.max(), p == p.min()
+            info["d_dr"] = float(d_dr)
             dp = dp + d_dr * (hi / hi.sum() - lo / lo.sum())
         return dp
 
+    # what the kernel-level tests of one scale compare besides sim, cs and dp (tests/test_hip_loss_kernels.py); d_dr and the tie
+    # counts are filled in by every backward() call
+    info = dict(dr=float(dr), from_p=bool(from_p), c1=float(c1), c2=float(c2), pmin=float(p.min()), pmax=float(p.max()),
+                tmin=float(t.min()), tmax=float(t.max()), vp_raw=vp_raw, vt_raw=vt_raw)
+    backward.info = info
     return sim, cs, backward
 
 

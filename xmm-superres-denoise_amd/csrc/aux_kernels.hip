@@ -309,18 +309,28 @@ __global__ void l1_loss_final_kernel(const double* partial, int nblocks, float* 
 // ---------------------------------------------------------------------------------------------------------------
 // torch.optim.Adam single step (model.py:241-245; lr/betas from res/configs/models.toml:7-8), fused over the flat
 // parameter buffer.  gscale folds the data-parallel 1/world_size mean into the read of the gradient.
+// The float operations are torch's own, in torch's order, each written out (no contraction left to the compiler: which
+// product of v * b2 + (1 - b2) * g * g it fuses changes the last bit of v):
+//   exp_avg.lerp_(grad, 1 - b1)                 m + w (g - m) fused for w < 0.5, g - (g - m)(1 - w) fused otherwise
+//   exp_avg_sq.mul_(b2).addcmul_(grad, grad, value = 1 - b2)     fma(((1 - b2) g), g, v b2)
+//   denom = exp_avg_sq.sqrt() / sqrt(bc2) + eps;  param.addcdiv_(exp_avg, denom, value = -lr / bc1)     p + (value m) / denom
+// m and v then equal torch's float32 CPU step bit for bit, p in about nine elements of ten (the others differ in the
+// last bit, where torch's vectorised sqrt or division rounds differently); tests/test_hip_optim_kernels.py prints the shares.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float lr_over_bc1, float inv_sqrt_bc2,
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, long long n, float neg_lr_over_bc1, float sqrt_bc2,
                             float b1, float b2, float eps, float gscale)
 {
+#pragma clang fp contract(off)      // the only fused operations are the two __fmaf_rn below
+    const float w1 = 1.f - b1, w2 = 1.f - b2;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+        const float gi = __fmul_rn(g[i], gscale);
+        const float d = __fsub_rn(gi, m[i]);
+        const float mi = w1 < 0.5f ? __fmaf_rn(d, w1, m[i]) : __fmaf_rn(-d, __fsub_rn(1.f, w1), gi);
+        const float vi = __fmaf_rn(__fmul_rn(w2, gi), gi, __fmul_rn(v[i], b2));
         m[i] = mi;
         v[i] = vi;
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        p[i] = p[i] - lr_over_bc1 * (mi / denom);
+        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vi), sqrt_bc2), eps);
+        p[i] = __fadd_rn(p[i], __fdiv_rn(__fmul_rn(neg_lr_over_bc1, mi), denom));
     }
 }
 
@@ -689,8 +699,8 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n
                        float eps, float gscale, hipStream_t s)
 {
     const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, p, g, m, v, n, (float)(lr / bc1),
-                       (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale);
+    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, p, g, m, v, n, (float)(-(double)lr / bc1),
+                       (float)sqrt(bc2), b1, b2, eps, gscale);
     return hipGetLastError();
 }
 hipError_t launch_pack_weights(const float* params, const PackDesc* descs_dev, int ndesc, float* fwd, float* bwd,

@@ -145,17 +145,24 @@ __global__ __launch_bounds__(NT) void ssim_kernel(const SsimParams P)
         st[r][c] = in ? tb[(long long)y * P.W + x] : 0.f;
     }
     __syncthreads();
-    // Variances and the covariance are shift invariant: the moments are taken about the tile's centre pixel (cp, ct), which
-    // removes the E[x^2] - mu^2 cancellation on nearly flat images (the coarse MS-SSIM scales); the means get it added back.
-    const float cp = sp[ext / 2][ext / 2], ct = st[ext / 2][ext / 2];
+    // Variances and the covariance are taken in two stages, each about the value at the centre of its own window, never as
+    // E[x^2] - mu^2 of the raw values: per row the moments of x - (the row window's centre pixel), then down the column the
+    // mean of the row variances plus the variance of the row means about the centre row's mean (var = E[var_row] +
+    // Var[mean_row]).  Every subtraction is between neighbours, so a window that is flat in an image has variance and
+    // covariance exactly 0 whatever its level (the zero background of an XMM frame, a saturated patch), and nearly flat
+    // images (the coarse MS-SSIM scales) lose nothing to cancellation.  A shift shared by the whole tile (its centre pixel)
+    // left (x - shift)^2 * 1e-7 of rounding in every window away from that value: 2e-5 of c2 per flat window, all of one sign.
+    const int R = P.taps.R;
     for (int i = threadIdx.x; i < ext * TS; i += NT) {
         const int r = i / TS, c = i - r * TS;
+        const float sx = sp[r][c + R], sy = st[r][c + R];
         float a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
         for (int k = 0; k <= R2; ++k) {
-            const float g = P.taps.g[k], x = sp[r][c + k] - cp, y = st[r][c + k] - ct;
+            const float g = P.taps.g[k], x = sp[r][c + k] - sx, y = st[r][c + k] - sy;
             a0 += g * x; a1 += g * y; a2 += g * (x * x); a3 += g * (y * y); a4 += g * (x * y);
         }
-        hz[0][r][c] = a0; hz[1][r][c] = a1; hz[2][r][c] = a2; hz[3][r][c] = a3; hz[4][r][c] = a4;
+        hz[0][r][c] = sx + a0; hz[1][r][c] = sy + a1;                       // row means
+        hz[2][r][c] = a2 - a0 * a0; hz[3][r][c] = a3 - a1 * a1; hz[4][r][c] = a4 - a0 * a1;   // row variances, row covariance
     }
     __syncthreads();
     const float c1 = P.sc->c1, c2 = P.sc->c2;
@@ -165,18 +172,19 @@ __global__ __launch_bounds__(NT) void ssim_kernel(const SsimParams P)
     double acc0 = 0, acc1 = 0;
     const int c = threadIdx.x & (TS - 1);
     for (int y = threadIdx.x / TS; y < TS; y += NT / TS) {
-        float mp = 0, mt = 0, epp = 0, ett = 0, ept = 0;
+        const float qp = hz[0][y + R][c], qt = hz[1][y + R][c];
+        float b0 = 0, b1 = 0, b2 = 0, b3 = 0, b4 = 0, wp = 0, wt = 0, wc = 0;
         for (int k = 0; k <= R2; ++k) {
-            const float g = P.taps.g[k];
-            mp += g * hz[0][y + k][c]; mt += g * hz[1][y + k][c]; epp += g * hz[2][y + k][c];
-            ett += g * hz[3][y + k][c]; ept += g * hz[4][y + k][c];
+            const float g = P.taps.g[k], ep = hz[0][y + k][c] - qp, et = hz[1][y + k][c] - qt;
+            b0 += g * ep; b1 += g * et; b2 += g * (ep * ep); b3 += g * (et * et); b4 += g * (ep * et);
+            wp += g * hz[2][y + k][c]; wt += g * hz[3][y + k][c]; wc += g * hz[4][y + k][c];
         }
         const int oy = oy0 + y, ox = ox0 + c;
         if (oy >= P.Hv || ox >= P.Wv) continue;
-        const float vp_raw = epp - mp * mp, vt_raw = ett - mt * mt;   // moments about (cp, ct)
+        const float vp_raw = wp + (b2 - b0 * b0), vt_raw = wt + (b3 - b1 * b1);
         const float vp = fmaxf(vp_raw, 0.f), vt = fmaxf(vt_raw, 0.f);
-        const float cov = ept - mp * mt;
-        mp += cp; mt += ct;                                           // the taps sum to 1
+        const float cov = wc + (b4 - b0 * b1);
+        float mp = qp + b0, mt = qt + b1;
         const float U = 2.f * cov + c2, L = vp + vt + c2;
         const float A = 2.f * mp * mt + c1, Bq = mp * mp + mt * mt + c1;
         const float cs = U / L, lum = A / Bq;
@@ -273,7 +281,7 @@ __global__ __launch_bounds__(NT) void combine_kernel(const CombineParams P)
             double raw = 0.0;
             for (int c = 0; c < G; ++c) raw += P.stat[((long long)s * P.B + (long long)smp * G + c) * 2 + (s == P.nscales - 1 ? 0 : 1)];
             raw /= G;
-            v[s] = raw > 0 ? raw : 0.0;                       // normalize="relu"
+            v[s] = raw <= 0 ? 0.0 : raw;                      // normalize="relu"; a NaN statistic stays NaN, as torch.relu keeps it
             M *= pow(v[s], (double)P.betas[s]);
         }
         acc += M;
@@ -492,6 +500,62 @@ int loss_check(const LossWeights& w, int B, int H, int W, const char** why)
     return 0;
 }
 
+// One scale of a chain: its images and the scratch its launches share.  scale_forward / scale_backward are the two loop bodies of
+// ssim_chain; the kernel-level test entry (loss_test_scale) runs the same two functions on one scale alone.
+struct ScaleRun {
+    const float* p; const float* t;
+    int B, H, W;
+    ScaleScal* sc;          // this scale's scalars
+    double* partial;        // [B * tiles][2]
+    float* mm_partial;      // [1024][4]
+    double* tie_partial;    // [1024][2]
+    float* maps;            // backward: [3][B][Hv][Wv]
+    Taps taps;
+    float k1, k2;
+};
+static int reduce_blocks(long long n) { const int g = grid_for(n, NT * 8); return g > 1024 ? 1024 : g; }
+static SsimParams ssim_params(const ScaleRun& r)
+{
+    const int R2 = 2 * r.taps.R;
+    SsimParams P;
+    P.p = r.p; P.t = r.t; P.B = r.B; P.H = r.H; P.W = r.W; P.Hv = r.H - R2; P.Wv = r.W - R2;
+    P.tilesX = (P.Wv + TS - 1) / TS; P.tilesY = (P.Hv + TS - 1) / TS;
+    P.sc = r.sc; P.partial = r.partial; P.gup = nullptr; P.maps = nullptr; P.taps = r.taps;
+    return P;
+}
+// minmax -> data_range, c1, c2 -> per-pixel statistics -> stat[B][2] = per-image mean (ssim, cs)
+static void scale_forward(const ScaleRun& r, double* stat, hipStream_t s)
+{
+    const long long n = (long long)r.B * r.H * r.W;
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(NT), 0, s, r.p, r.t, n, r.mm_partial);
+    hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(NT), 0, s, r.mm_partial, nb, r.sc, r.k1, r.k2);
+    const SsimParams P = ssim_params(r);
+    hipLaunchKernelGGL(ssim_kernel<false>, dim3(P.tilesX, P.tilesY, r.B), dim3(NT), 0, s, P);
+    hipLaunchKernelGGL(image_stat_kernel, dim3(r.B), dim3(NT), 0, s, r.partial, P.tilesX * P.tilesY, 1.0 / ((double)P.Hv * P.Wv), stat);
+}
+// tie counts -> gradient maps -> d loss / d data_range -> transpose filter onto out [B][H][W] (+ the pooled scale's gradient `coarse`)
+static void scale_backward(const ScaleRun& r, const float* gup, const float* coarse, int Hc, int Wc, float* out, int accumulate, hipStream_t s)
+{
+    const long long n = (long long)r.B * r.H * r.W;
+    const int nb = reduce_blocks(n);
+    hipLaunchKernelGGL(ties_kernel, dim3(nb), dim3(NT), 0, s, r.p, n, r.sc, r.tie_partial);
+    SsimParams P = ssim_params(r);
+    P.gup = gup; P.maps = r.maps;
+    hipLaunchKernelGGL(ssim_kernel<true>, dim3(P.tilesX, P.tilesY, r.B), dim3(NT), 0, s, P);
+    hipLaunchKernelGGL(scale_bwd_scalars_kernel, dim3(1), dim3(NT), 0, s, r.partial, r.B * P.tilesX * P.tilesY, r.tie_partial, nb, r.sc, r.k1,
+                       r.k2);
+    BackFilterParams F;
+    F.p = r.p; F.t = r.t; F.maps = r.maps; F.B = r.B; F.H = r.H; F.W = r.W; F.Hv = P.Hv; F.Wv = P.Wv; F.sc = r.sc;
+    F.coarse = coarse; F.Hc = coarse ? Hc : 0; F.Wc = coarse ? Wc : 0;
+    F.out = out; F.accumulate = accumulate; F.taps = r.taps;
+    hipLaunchKernelGGL(back_filter_kernel, dim3((r.W + TS - 1) / TS, (r.H + TS - 1) / TS, r.B), dim3(NT), 0, s, F);
+}
+static void pool2(const float* p, const float* t, float* po, float* to, int B, int H, int W, hipStream_t s)
+{
+    hipLaunchKernelGGL(pool2_kernel, dim3(grid_for((long long)B * (H / 2) * (W / 2), 256)), dim3(256), 0, s, p, t, po, to, B, H, W, H / 2, W / 2);
+}
+
 // One SSIM chain (nscales = 1: plain SSIM, 5: MS-SSIM).  ws is carved linearly; everything is stream-ordered.
 static hipError_t ssim_chain(const LossWeights& w, int term, int nscales, const float* y, const float* t, float* dy, int accumulate,
                              float* out8, int B, int group, int H, int W, char* ws, hipStream_t s)
@@ -509,30 +573,22 @@ static hipError_t ssim_chain(const LossWeights& w, int term, int nscales, const 
         const size_t b = (size_t)B * Hs[k] * Ws[k] * 4;
         float* pk = (float*)carve(b); float* tk = (float*)carve(b);
         ps[k] = pk; ts[k] = tk; gs[k] = dy ? (float*)carve(b) : nullptr;
-        hipLaunchKernelGGL(pool2_kernel, dim3(grid_for((long long)B * Hs[k] * Ws[k], 256)), dim3(256), 0, s, ps[k - 1], ts[k - 1], pk, tk, B,
-                           Hs[k - 1], Ws[k - 1], Hs[k], Ws[k]);
+        pool2(ps[k - 1], ts[k - 1], pk, tk, B, Hs[k - 1], Ws[k - 1], s);
     }
     ScaleScal* sc = (ScaleScal*)carve(sizeof(ScaleScal) * LOSS_MAX_SCALES);
     double* stat = (double*)carve(sizeof(double) * 2 * B * LOSS_MAX_SCALES);
     float* gup = (float*)carve(sizeof(float) * 2 * B * LOSS_MAX_SCALES);
     const int maxtiles = ((H + TS - 1) / TS) * ((W + TS - 1) / TS);
-    double* partial = (double*)carve(sizeof(double) * 2 * (size_t)B * maxtiles);
-    float* mm_partial = (float*)carve(sizeof(float) * 4 * 1024);
-    double* tie_partial = (double*)carve(sizeof(double) * 2 * 1024);
-    float* maps = dy ? (float*)carve((size_t)3 * B * (H - R2) * (W - R2) * 4) : nullptr;
+    ScaleRun r;
+    r.B = B; r.taps = taps; r.k1 = w.k1; r.k2 = w.k2;
+    r.partial = (double*)carve(sizeof(double) * 2 * (size_t)B * maxtiles);
+    r.mm_partial = (float*)carve(sizeof(float) * 4 * 1024);
+    r.tie_partial = (double*)carve(sizeof(double) * 2 * 1024);
+    r.maps = dy ? (float*)carve((size_t)3 * B * (H - R2) * (W - R2) * 4) : nullptr;
 
     for (int k = 0; k < nscales; ++k) {
-        const long long n = (long long)B * Hs[k] * Ws[k];
-        const int nb = grid_for(n, NT * 8) > 1024 ? 1024 : grid_for(n, NT * 8);
-        hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(NT), 0, s, ps[k], ts[k], n, mm_partial);
-        hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(NT), 0, s, mm_partial, nb, sc + k, w.k1, w.k2);
-        SsimParams P;
-        P.p = ps[k]; P.t = ts[k]; P.B = B; P.H = Hs[k]; P.W = Ws[k]; P.Hv = Hs[k] - R2; P.Wv = Ws[k] - R2;
-        P.tilesX = (P.Wv + TS - 1) / TS; P.tilesY = (P.Hv + TS - 1) / TS;
-        P.sc = sc + k; P.partial = partial; P.gup = nullptr; P.maps = nullptr; P.taps = taps;
-        hipLaunchKernelGGL(ssim_kernel<false>, dim3(P.tilesX, P.tilesY, B), dim3(NT), 0, s, P);
-        hipLaunchKernelGGL(image_stat_kernel, dim3(B), dim3(NT), 0, s, partial, P.tilesX * P.tilesY, 1.0 / ((double)P.Hv * P.Wv),
-                           stat + (size_t)k * 2 * B);
+        r.p = ps[k]; r.t = ts[k]; r.H = Hs[k]; r.W = Ws[k]; r.sc = sc + k;
+        scale_forward(r, stat + (size_t)k * 2 * B, s);
     }
     CombineParams C;
     C.stat = stat; C.nscales = nscales; C.B = B; C.group = group; C.ms = nscales > 1; C.weight = w.w[term]; C.value = out8 + 1 + term; C.gup = gup;
@@ -540,23 +596,52 @@ static hipError_t ssim_chain(const LossWeights& w, int term, int nscales, const 
     hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(NT), 0, s, C);
     if (dy) {
         for (int k = nscales - 1; k >= 0; --k) {
-            const long long n = (long long)B * Hs[k] * Ws[k];
-            const int nb = grid_for(n, NT * 8) > 1024 ? 1024 : grid_for(n, NT * 8);
-            hipLaunchKernelGGL(ties_kernel, dim3(nb), dim3(NT), 0, s, ps[k], n, sc + k, tie_partial);
-            SsimParams P;
-            P.p = ps[k]; P.t = ts[k]; P.B = B; P.H = Hs[k]; P.W = Ws[k]; P.Hv = Hs[k] - R2; P.Wv = Ws[k] - R2;
-            P.tilesX = (P.Wv + TS - 1) / TS; P.tilesY = (P.Hv + TS - 1) / TS;
-            P.sc = sc + k; P.partial = partial; P.gup = gup + (size_t)k * 2 * B; P.maps = maps; P.taps = taps;
-            hipLaunchKernelGGL(ssim_kernel<true>, dim3(P.tilesX, P.tilesY, B), dim3(NT), 0, s, P);
-            hipLaunchKernelGGL(scale_bwd_scalars_kernel, dim3(1), dim3(NT), 0, s, partial, B * P.tilesX * P.tilesY, tie_partial, nb, sc + k,
-                               w.k1, w.k2);
-            BackFilterParams F;
-            F.p = ps[k]; F.t = ts[k]; F.maps = maps; F.B = B; F.H = Hs[k]; F.W = Ws[k]; F.Hv = P.Hv; F.Wv = P.Wv; F.sc = sc + k;
-            F.coarse = k + 1 < nscales ? gs[k + 1] : nullptr; F.Hc = k + 1 < nscales ? Hs[k + 1] : 0; F.Wc = k + 1 < nscales ? Ws[k + 1] : 0;
-            F.out = gs[k]; F.accumulate = k == 0 ? accumulate : 0; F.taps = taps;
-            hipLaunchKernelGGL(back_filter_kernel, dim3((Ws[k] + TS - 1) / TS, (Hs[k] + TS - 1) / TS, B), dim3(NT), 0, s, F);
+            r.p = ps[k]; r.t = ts[k]; r.H = Hs[k]; r.W = Ws[k]; r.sc = sc + k;
+            const bool has_coarse = k + 1 < nscales;
+            scale_backward(r, gup + (size_t)k * 2 * B, has_coarse ? gs[k + 1] : nullptr, has_coarse ? Hs[k + 1] : 0, has_coarse ? Ws[k + 1] : 0,
+                           gs[k], k == 0 ? accumulate : 0, s);
         }
     }
+    return hipGetLastError();
+}
+
+// ---- kernel-level test entries (xsd_loss_test_scale / xsd_loss_test_pool2, include/xsd.h; no product path calls these) -------------
+// One scale exactly as ssim_chain runs it, on a workspace of its own; synchronous.  scal11: pmin, pmax, tmin, tmax, dr, c1, c2, from_p,
+// nmax, nmin, ddr of the scale's ScaleScal as it stands after the last launch.
+hipError_t loss_test_scale(const LossWeights& w, const float* y, const float* t, const float* gup, const float* coarse, float* dy,
+                           int accumulate, double* stat, float* scal11, int B, int H, int W, hipStream_t s)
+{
+    const Taps taps = make_taps(w.sigma);
+    const int R2 = 2 * taps.R;
+    const size_t ntiles = (size_t)((H + TS - 1) / TS) * ((W + TS - 1) / TS);
+    const size_t sizes[5] = {sizeof(ScaleScal), sizeof(double) * 2 * B * ntiles, sizeof(float) * 4 * 1024, sizeof(double) * 2 * 1024,
+                             dy ? (size_t)3 * B * (H - R2) * (W - R2) * 4 : 0};
+    size_t total = 0;
+    for (size_t b : sizes) total += (b + 255) & ~(size_t)255;
+    char* ws = nullptr;
+    hipError_t err = hipMalloc((void**)&ws, total);
+    if (err != hipSuccess) return err;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { char* p = ws + off; off += (bytes + 255) & ~(size_t)255; return p; };
+    ScaleRun r;
+    r.p = y; r.t = t; r.B = B; r.H = H; r.W = W; r.taps = taps; r.k1 = w.k1; r.k2 = w.k2;
+    r.sc = (ScaleScal*)carve(sizes[0]); r.partial = (double*)carve(sizes[1]); r.mm_partial = (float*)carve(sizes[2]);
+    r.tie_partial = (double*)carve(sizes[3]); r.maps = dy ? (float*)carve(sizes[4]) : nullptr;
+    scale_forward(r, stat, s);
+    if (dy) scale_backward(r, gup, coarse, H / 2, W / 2, dy, accumulate, s);
+    err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    ScaleScal h;
+    if (err == hipSuccess) err = hipMemcpy(&h, r.sc, sizeof(h), hipMemcpyDeviceToHost);
+    hipFree(ws);
+    if (err != hipSuccess) return err;
+    const float out[11] = {h.pmin, h.pmax, h.tmin, h.tmax, h.dr, h.c1, h.c2, (float)h.from_p, h.nmax, h.nmin, h.ddr};
+    for (int i = 0; i < 11; ++i) scal11[i] = out[i];
+    return hipSuccess;
+}
+hipError_t loss_test_pool2(const float* p, const float* t, float* po, float* to, int B, int H, int W, hipStream_t s)
+{
+    pool2(p, t, po, to, B, H, W, s);
     return hipGetLastError();
 }
 

@@ -1837,4 +1837,45 @@ int xsd_test_gpack(int nconv, const int* host_cout, const int* host_cin, const f
     return XSD_OK;
 }
 
+// ---- the loss kernels scale by scale, the pooling and the plane path's clamp backward (include/xsd.h) ----
+int xsd_loss_test_scale(const xsd_loss_config* cfg, const float* dev_y, const float* dev_target, const float* dev_gup, const float* dev_coarse,
+                        float* dev_dy, int accumulate, double* dev_stat, float* host_scal11, int B, int H, int W, void* stream)
+{
+    if (!cfg || !dev_y || !dev_target || !dev_stat || !host_scal11) return fail(XSD_ERR_ARG, "null argument");
+    if (!(cfg->sigma > 0.f)) return fail(XSD_ERR_ARG, "loss: sigma must be > 0");
+    if ((dev_dy != nullptr) != (dev_gup != nullptr)) return fail(XSD_ERR_ARG, "dy and the upstream pair come together");
+    if (dev_coarse && !dev_dy) return fail(XSD_ERR_ARG, "a coarse gradient needs dy");
+    LossWeights w;
+    for (int i = 0; i < 5; ++i) w.w[i] = 0.f;
+    w.w[3] = 1.f;                                  // what loss_check refuses for ssim
+    w.correction = 0.f; w.sigma = cfg->sigma; w.k1 = cfg->k1; w.k2 = cfg->k2; w.kernel_size = cfg->kernel_size;
+    const char* why = nullptr;
+    if (loss_check(w, B, H, W, &why)) return fail(XSD_ERR_ARG, why);
+    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
+    hipError_t err = loss_test_scale(w, dev_y, dev_target, dev_gup, dev_coarse, dev_dy, accumulate, dev_stat, host_scal11, B, H, W, (hipStream_t)stream);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "loss scale: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_loss_test_pool2(const float* dev_p, const float* dev_t, float* dev_po, float* dev_to, int B, int H, int W, void* stream)
+{
+    if (!dev_p || !dev_t || !dev_po || !dev_to || B < 1 || H < 2 || W < 2) return fail(XSD_ERR_ARG, "null argument or an image under 2 x 2");
+    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t err = loss_test_pool2(dev_p, dev_t, dev_po, dev_to, B, H, W, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "pool2: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_clamp_bwd(const float* dev_pre, const float* dev_dy, float* dev_dpre, int64_t n, void* stream)
+{
+    if (!dev_pre || !dev_dy || !dev_dpre || n <= 0) return fail(XSD_ERR_ARG, "null argument or n <= 0");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t err = launch_clamp_bwd(dev_pre, dev_dy, dev_dpre, n, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "clamp backward: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
 } // extern "C"

@@ -26,4 +26,11 @@ int loss_check(const LossWeights& w, int B, int H, int W, const char** why);
 hipError_t launch_loss(const LossWeights& w, const float* y, const float* t, float* dy, float* out8, int B, int channels, int H, int W,
                        void* workspace, hipStream_t s);
 
+// Kernel-level test entries (include/xsd.h: xsd_loss_test_scale, xsd_loss_test_pool2).  loss_test_scale: ONE SSIM scale through the two
+// host functions ssim_chain runs per scale (forward; with dy also backward: gup [B][2], coarse [B][H / 2][W / 2] or null); synchronous,
+// allocates its own scratch; stat [B][2] device doubles, scal11 host floats.  loss_test_pool2: the 2 x 2 average pooling of both images.
+hipError_t loss_test_scale(const LossWeights& w, const float* y, const float* t, const float* gup, const float* coarse, float* dy,
+                           int accumulate, double* stat, float* scal11, int B, int H, int W, hipStream_t s);
+hipError_t loss_test_pool2(const float* p, const float* t, float* po, float* to, int B, int H, int W, hipStream_t s);
+
 } // namespace xsd
