@@ -173,6 +173,25 @@ int xsd_ext_metrics_create(xsd_ext_metrics** out);
 void xsd_ext_metrics_destroy(xsd_ext_metrics* m);
 int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float* dev_target, double* dev_out, int B, int H, int W,
                          void* stream);
+/* Test entry, in the product library like xsd_loss_test_scale: after an xsd_ext_metrics_eval on the handle, copy ONE region of that
+ * eval's workspace into dev_dst (device memory, dst_bytes long) on `stream` (the eval's stream, or one ordered after it).  The offsets
+ * come from the same host function the eval lays its workspace out with.  Images (fp32, [B][h][w]; side 0 = preds, 1 = target):
+ *   U1..U3  the pool2 chain (GMSD / MS-GMSD scales 1..3, HaarPSI's input)      M  MDSI's k x k mean      V1..V3  VIF's chain, scales 1..3.
+ * Tile partials (doubles, [B][ntiles][entries]; `side` must still be 0 or 1 and is otherwise ignored), tiles in row-major order:
+ *   GMS0..3   4 entries: sum g, sum g^2 (MS-GMSD form), sum g, sum g^2 (GMSD form; zeros except at scale 1); 4 x 64 tiles of the scale's map
+ *   HAAR      2: sum sigmoid * weight, sum weight (both orientations); 4 x 64 tiles of U1
+ *   MDSI1     2: sum re, sum im;    MDSI2   1: sum |z - mean z|; 4 x 64 tiles of M
+ *   VIF0..3   2: numerator, denominator; 16 x 16 WINDOWS per tile of the scale's valid-window map.
+ * info (8 host ints, filled whenever the handle, the stage and the side are accepted -- also when the buffer is then refused as too
+ * small, so a caller can size it): [0] B  [1] rows  [2] columns of the image or of the map the tiles cover (windows for VIF)
+ * [3] entries per tile (0: an image)  [4] tiles_x  [5] ntiles per image  [6] tile rows  [7] tile columns ([4..7] are 0 for images).
+ * Refused with XSD_ERR_ARG: null pointers, an unknown stage or side, a buffer too small, a handle that has not evaluated. */
+enum {
+    XSD_EXTM_STAGE_U1 = 0, XSD_EXTM_STAGE_U2, XSD_EXTM_STAGE_U3, XSD_EXTM_STAGE_M, XSD_EXTM_STAGE_V1, XSD_EXTM_STAGE_V2, XSD_EXTM_STAGE_V3,
+    XSD_EXTM_STAGE_GMS0, XSD_EXTM_STAGE_GMS1, XSD_EXTM_STAGE_GMS2, XSD_EXTM_STAGE_GMS3, XSD_EXTM_STAGE_HAAR, XSD_EXTM_STAGE_MDSI1,
+    XSD_EXTM_STAGE_MDSI2, XSD_EXTM_STAGE_VIF0, XSD_EXTM_STAGE_VIF1, XSD_EXTM_STAGE_VIF2, XSD_EXTM_STAGE_VIF3, XSD_EXTM_STAGES
+};
+int xsd_ext_metrics_test_stage(xsd_ext_metrics* m, int stage, int side, void* dev_dst, int64_t dst_bytes, int* info, void* stream);
 
 /* The sixth extended test metric: piq 0.7.x fsim(x, y, chromatic=False) with every default (data_range=1, scales=4, orientations=4,
  * min_length=6, mult=2, sigma_f=0.55, delta_theta=1.2, k=2.0) on single-channel images in [0, 1], restated from piq's published code
@@ -203,6 +222,22 @@ int xsd_fsim_eval(xsd_fsim* m, const float* dev_preds, const float* dev_target, 
  * (the engine's own rows are squares, never negative). */
 int xsd_fsim_test_dft2(xsd_fsim* m, const float* dev_in, float* dev_out, int B, int n1, int n2, int inverse, void* stream);
 int xsd_fsim_test_median(const float* dev_in, float* dev_out, int rows, int n, void* stream);
+/* test_stage: after an xsd_fsim_eval on the handle, copy ONE region of that eval's workspace, or of the plan it used, into dev_dst
+ * (device memory, dst_bytes long) on `stream`; the offsets come from the host function the eval lays its workspace out with.
+ * sb = s * B + image, s = 0 preds, 1 target; NO = 4 orientations, NF = 16 filters (index o * 4 + scale):
+ *   POOLED  double [2B][h][w]          EO    float (re, im) [2B][NF][h][w]      EN, AN  double [2B][NO][h][w]
+ *   A0SQ    float [2B][NO][h][w]       T     double [2B][NO]                    PART    double [B][ntiles][2], 4 x 64 tiles, row-major
+ *   FILT    double [NF][h][w] (plan)   NOISE double [3][NO]: em_n, sum_an2, sum_ai_aj (plan).
+ * info (8 host ints, filled whenever the handle and the stage are accepted, also when the buffer is then refused as too small):
+ * [0] the leading count (2B, B, NF or 3)  [1] h  [2] w  [3] entries per tile (PART: 2, else 0)  [4] tiles_x  [5] ntiles  [6] tile rows
+ * [7] tile columns ([4..7] are 0 except for PART).
+ * Refused with XSD_ERR_ARG: null pointers, an unknown stage, a buffer too small, a handle that has not evaluated (or whose plan of that
+ * eval has since been evicted by XSD_FSIM_PLANS other sizes). */
+enum {
+    XSD_FSIM_STAGE_POOLED = 0, XSD_FSIM_STAGE_EO, XSD_FSIM_STAGE_EN, XSD_FSIM_STAGE_AN, XSD_FSIM_STAGE_A0SQ, XSD_FSIM_STAGE_T,
+    XSD_FSIM_STAGE_PART, XSD_FSIM_STAGE_FILT, XSD_FSIM_STAGE_NOISE, XSD_FSIM_STAGES
+};
+int xsd_fsim_test_stage(xsd_fsim* m, int stage, void* dev_dst, int64_t dst_bytes, int* info, void* stream);
 
 /* torch.optim.Adam(lr, betas, eps=1e-8) single fused step over flat buffers (models/model.py:241-245).
  * step is 1-based; grad_scale multiplies the gradient on read (1/world_size for data-parallel mean). */

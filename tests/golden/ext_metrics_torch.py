@@ -177,6 +177,94 @@ def vif_p(x, y):
     return n / d
 
 
+# ---- the same formulas returning MAPS, not sums: the per-stage yardstick of tests/test_hip_ext_metrics_kernels.py.  Every map is
+# [B, h, w] in the dtype of the inputs; reduced, they are the functions above (tests/test_hip_ext_metrics_kernels.py asserts it).
+def pool_levels(x):
+    """[pool2(x), pool2^2(x), pool2^3(x)] of a [B, H, W] image, each [B, h, w]"""
+    out, u = [], _b1hw(x)
+    for _ in range(3):
+        u = pool2(u)
+        out.append(u[:, 0])
+    return out
+
+
+def gms_maps(x, y, alpha=0.5, t=170.0):
+    """([MS-GMSD's similarity map at scales 0..3], GMSD's similarity map (on the once-pooled [0, 1] image))"""
+    a, b = 255 * _b1hw(x), 255 * _b1hw(y)
+    ms = []
+    for k in range(4):
+        if k > 0:
+            a, b = pool2(a), pool2(b)
+        ga, gb = prewitt_grad(a), prewitt_grad(b)
+        ms.append((((2 - alpha) * ga * gb + t) / (ga ** 2 + gb ** 2 - alpha * ga * gb + t))[:, 0])
+    a, b = pool2(_b1hw(x)), pool2(_b1hw(y))
+    t1 = 170 / 255 ** 2
+    ga, gb = prewitt_grad(a), prewitt_grad(b)
+    return ms, ((2 * ga * gb + t1) / (ga ** 2 + gb ** 2 + t1))[:, 0]
+
+
+def haarpsi_maps(x, y, c=30.0, alpha=4.2):
+    """(sum_o sigmoid(alpha S_o) w_o, sum_o w_o) per pixel of the once-pooled image"""
+    x, y = pool2(255 * _b1hw(x)), pool2(255 * _b1hw(y))
+    cx = [haar_coefficients(x, s).abs() for s in range(3)]
+    cy = [haar_coefficients(y, s).abs() for s in range(3)]
+    w = torch.maximum(cx[2], cy[2])
+    s = (sim(cx[0], cy[0], c) + sim(cx[1], cy[1], c)) / 2
+    return (torch.sigmoid(alpha * s) * w).sum(1), w.sum(1)
+
+
+def mdsi_maps(x, y, c1=140.0, c2=55.0, c3=550.0, alpha=0.6, q=0.25):
+    """(pooled x, pooled y, re z, im z, |z - mean z|) with z = G^q as a complex power"""
+    x, y = mdsi_pool(_b1hw(x)), mdsi_pool(_b1hw(y))
+    lx, hx, mx = 0.9999 * (255 * x), -0.01 * (255 * x), -0.09 * (255 * x)
+    ly, hy, my = 0.9999 * (255 * y), -0.01 * (255 * y), -0.09 * (255 * y)
+    gx, gy, ga = prewitt_grad(lx), prewitt_grad(ly), prewitt_grad((lx + ly) / 2)
+    gs = sim(gx, gy, c1) + sim(gx, ga, c2) - sim(gy, ga, c2)
+    cs = (2 * (hx * hy + mx * my) + c3) / (hx ** 2 + hy ** 2 + mx ** 2 + my ** 2 + c3)
+    re, im = complex_power(alpha * gs + (1 - alpha) * cs, q)
+    mre, mim = re.mean(dim=[1, 2, 3], keepdim=True), im.mean(dim=[1, 2, 3], keepdim=True)
+    return x[:, 0], y[:, 0], re[:, 0], im[:, 0], torch.sqrt((re - mre) ** 2 + (im - mim) ** 2)[:, 0]
+
+
+def vif_maps(x, y, sigma_n_sq=2.0):
+    """per scale 0..3: (preds image, target image, numerator map, denominator map); the maps are over the valid windows"""
+    p, t = _b1hw(x), _b1hw(y)
+    eps = 1e-10
+    out = []
+    for s in range(4):
+        n = 2 ** (4 - s) + 1
+        k = vif_kernel(n, p.dtype, p.device)
+        if s > 0:
+            t, p = F.conv2d(t, k)[:, :, ::2, ::2], F.conv2d(p, k)[:, :, ::2, ::2]
+        mu_t, mu_p = F.conv2d(t, k), F.conv2d(p, k)
+        st = torch.clamp(F.conv2d(t ** 2, k) - mu_t ** 2, min=0.0)
+        sp = torch.clamp(F.conv2d(p ** 2, k) - mu_p ** 2, min=0.0)
+        stp = F.conv2d(t * p, k) - mu_t * mu_p
+        g = stp / (st + eps)
+        sv = sp - g * stp
+        m = st < eps
+        g = torch.where(m, torch.zeros_like(g), g)
+        sv = torch.where(m, sp, sv)
+        st = torch.where(m, torch.zeros_like(st), st)
+        m = sp < eps
+        g = torch.where(m, torch.zeros_like(g), g)
+        sv = torch.where(m, torch.zeros_like(sv), sv)
+        m = g < 0
+        sv = torch.where(m, sp, sv)
+        g = torch.where(m, torch.zeros_like(g), g)
+        sv = torch.clamp(sv, min=eps)
+        out.append((p[:, 0], t[:, 0], torch.log10(1.0 + g ** 2 * st / (sv + sigma_n_sq))[:, 0], torch.log10(1.0 + st / sigma_n_sq)[:, 0]))
+    return out
+
+
+def tile_sums(m, th, tw):
+    """[B, h, w] -> [B, ntiles]: the sum over each th x tw tile, tiles in row-major order (the last row / column of tiles may be partial)"""
+    B, h, w = m.shape
+    ny, nx = -(-h // th), -(-w // tw)
+    m = F.pad(m, [0, nx * tw - w, 0, ny * th - h])
+    return m.reshape(B, ny, th, nx, tw).sum(dim=[2, 4]).reshape(B, ny * nx)
+
+
 FUNCS = {"vif_p": vif_p, "gmsd": gmsd, "ms_gmsd": ms_gmsd, "haarpsi": haarpsi, "msdi": msdi}
 
 

@@ -147,6 +147,48 @@ def fsim(x, y):
     return n / d
 
 
+# ---- the same formulas returning every intermediate MAP: the per-stage yardstick of tests/test_hip_fsim_kernels.py (reduced, they are
+# the functions above; that file asserts it)
+def pc_maps(img):
+    """img [B,1,h,w] (pooled, 255-scaled) -> dict: eo [B,O,S,h,w] complex; en [B,O,h,w] the energy BEFORE its threshold; an [B,O,h,w] the
+    sum over the scales of |eo|; a0sq [B,O,h,w] = |eo[:, :, 0]|^2 (what the median is taken of); T [B,O]; pc [B,h,w]"""
+    eps = torch.finfo(img.dtype).eps
+    B, _, h, w = img.shape
+    filters = construct_filters(h, w, img.dtype).to(img.device)
+    em_n, sum_an2, sum_ai_aj = (c.reshape(1, ORIENTATIONS, 1, 1) for c in noise_constants(filters))
+    eo = torch.fft.ifft2(torch.fft.fft2(img)[:, :, None] * filters[None])
+    even, odd = eo.real, eo.imag
+    an = torch.sqrt(even ** 2 + odd ** 2)
+    sum_e, sum_o = even.sum(2, keepdim=True), odd.sum(2, keepdim=True)
+    x_energy = torch.sqrt(sum_e ** 2 + sum_o ** 2) + eps
+    mean_e, mean_o = sum_e / x_energy, sum_o / x_energy
+    en = (even * mean_e + odd * mean_o - torch.abs(even * mean_o - odd * mean_e)).sum(2)
+    a0sq = an[:, :, 0] ** 2
+    T = threshold(torch.median(a0sq.reshape(B, ORIENTATIONS, h * w), dim=-1).values.reshape(B, ORIENTATIONS, 1, 1), em_n, sum_an2, sum_ai_aj)
+    pc = torch.max(en - T, torch.zeros_like(en)).sum(1) / an.sum(dim=[1, 2])
+    return {"eo": eo, "en": en, "an": an.sum(2), "a0sq": a0sq, "T": T.reshape(B, ORIENTATIONS), "pc": pc}
+
+
+def threshold(median_e2n, em_n, sum_an2, sum_ai_aj):
+    """the noise threshold T of an orientation from the median of |eo[o, 0]|^2 and the orientation's three noise constants"""
+    mean_e2n = -median_e2n / math.log(0.5)
+    noise_power = mean_e2n / em_n
+    noise_energy2 = 2 * noise_power * sum_an2 + 4 * noise_power * sum_ai_aj
+    tau = torch.sqrt(noise_energy2 / 2)
+    return (tau * math.sqrt(math.pi / 2) + K * torch.sqrt((2 - math.pi / 2) * tau ** 2)) / 1.7
+
+
+def fsim_maps(x, y):
+    """dict: pooled [2][B,h,w] (preds, target); pc [2] of pc_maps' dicts; num = GM * PC * pc_max and den = pc_max, each [B,h,w]"""
+    x, y = pool(_b1hw(x)), pool(_b1hw(y))
+    mx, my = pc_maps(x), pc_maps(y)
+    pc_x, pc_y = mx["pc"][:, None], my["pc"][:, None]
+    g_x, g_y = scharr_grad(x), scharr_grad(y)
+    pc_max = torch.where(pc_x > pc_y, pc_x, pc_y)
+    score = sim(g_x, g_y, T2) * sim(pc_x, pc_y, T1) * pc_max
+    return {"pooled": (x[:, 0], y[:, 0]), "pc": (mx, my), "num": score[:, 0], "den": pc_max[:, 0]}
+
+
 def photon_pair(shape, gen, dtype=torch.float64, rate=0.3, noise=0.05):
     """photon-like test pair, made as tests/test_hip_ext_metrics.py makes its pairs: target = 3x3-smoothed clamped Poisson counts,
     prediction = target + noise clamped to [0, 1]"""

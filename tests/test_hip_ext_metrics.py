@@ -40,7 +40,11 @@ def _case(size):
         H, W = SIZES[size]
         p, t = E.photon_pair((4, H, W), torch.Generator().manual_seed(100 + H + W))
         p, t = p.float(), t.float()
-        _cache[size] = (p, t, E.all_metrics(p.double(), t.double()), E.all_metrics(p, t))
+        m64, m32 = E.all_metrics(p.double(), t.double()), E.all_metrics(p, t)
+        # vif_p's numerator and denominator on their own too: an error common to both cancels in the ratio
+        m64["vif_num"], m64["vif_den"] = E.vif_parts(p.double(), t.double())
+        m32["vif_num"], m32["vif_den"] = E.vif_parts(p, t)
+        _cache[size] = (p, t, m64, m32)
     return _cache[size]
 
 
@@ -59,9 +63,11 @@ def engine():
 @pytest.mark.parametrize("size", list(SIZES))
 def test_accuracy_against_the_float64_restatement(engine, size, B):
     p, t, m64, m32 = _case(size)
-    got = _named(engine.eval(p[:B].to(DEV), t[:B].to(DEV)))
+    out = engine.eval(p[:B].to(DEV), t[:B].to(DEV))
+    got = _named(out)
+    got["vif_num"], got["vif_den"] = out[:, 4].cpu(), out[:, 5].cpu()
     misses = []
-    for n in E.NAMES:
+    for n in E.NAMES + ("vif_num", "vif_den"):
         for b in range(B):
             g, f64, f32 = got[n][b].item(), m64[n][b].item(), float(m32[n][b].item())
             bar = _bar(f32, f64)

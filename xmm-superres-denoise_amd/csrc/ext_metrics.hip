@@ -384,66 +384,83 @@ __global__ __launch_bounds__(NT) void mdsi_kernel(Plane P, const double* __restr
 }
 
 // ---- 10: VIF's per-scale statistics over valid N x N windows, one workgroup per 16 x 16 windows.  The (16 + N - 1)^2 pixels under them
-// go to LDS once, as differences from the tile's first pixel (variance and covariance do not move with the origin; fp32 then sums
-// small numbers instead of cancelling two large ones); the Gaussian is the outer product of its 1-D form, so the five moments are
-// one horizontal pass into LDS and one vertical pass per window.
+// go to LDS once; the Gaussian is the outer product of its 1-D form, so the statistics are one horizontal pass into LDS and one
+// vertical pass per window.
+// Variances and the covariance are taken in two stages, each about the value at the centre of its own window, never as E[x^2] - mu^2
+// of the raw values (as ssim_kernel of loss_kernels.hip): per row the moments of x - (the row window's centre pixel), then down the
+// column the mean of the row variances plus the variance of the row means about the centre row's mean (var = E[var_row] +
+// Var[mean_row]).  Every subtraction is between neighbours, so a window over a flat region has variance and covariance exactly 0
+// whatever its level (the zero background of an XMM frame).  An origin shared by the whole tile (its first pixel, as this kernel had
+// it) left (x - origin)^2 * 1e-7 of rounding in every window away from that value: with a source on a tile's first pixel and zero
+// background under the rest, 2e-8 per window, all of one sign -- 7e-5 to 9e-5 of the two sums of an 80 x 80 image, 4.7 times the bar.
 constexpr int VT = 16;                   // windows per tile side
 constexpr int VIN = VT + 17 - 1;         // largest pixel tile side (17 taps)
 constexpr int VSTRIDE = VIN + 1;         // row stride in LDS: odd, so the horizontal pass's four rows per wave fall on different banks
 
+// m = var t, var p, cov(t, p) of this thread's window
 template <int N>
 __device__ __forceinline__ void vif_tile(const float* __restrict__ t, const float* __restrict__ p, int h, int w, int i0, int j0,
                                          const float* __restrict__ g, float* __restrict__ sa, float* __restrict__ sc, float* __restrict__ hq,
-                                         float (&m)[5])
+                                         float (&m)[3])
 {
-    constexpr int IN = VT + N - 1;
+    constexpr int IN = VT + N - 1, R = N / 2;
     const int tid = threadIdx.y * TW + threadIdx.x;
-    const float ct = t[(size_t)i0 * w + j0], cp = p[(size_t)i0 * w + j0];
     for (int k = tid; k < IN * IN; k += NT) {
         const int r = k / IN, c = k % IN, ii = i0 + r, jj = j0 + c;
         const bool in = ii < h && jj < w;          // pixels past the image only feed windows that are not counted
-        sa[r * VSTRIDE + c] = in ? t[(size_t)ii * w + jj] - ct : 0.f;
-        sc[r * VSTRIDE + c] = in ? p[(size_t)ii * w + jj] - cp : 0.f;
+        sa[r * VSTRIDE + c] = in ? t[(size_t)ii * w + jj] : 0.f;
+        sc[r * VSTRIDE + c] = in ? p[(size_t)ii * w + jj] : 0.f;
     }
     __syncthreads();
     for (int k = tid; k < IN * VT; k += NT) {
         const int r = k / VT, c = k % VT;
+        const float ca = sa[r * VSTRIDE + c + R], cq = sc[r * VSTRIDE + c + R];
         float rt = 0.f, rp = 0.f, rtt = 0.f, rpp = 0.f, rtp = 0.f;
 #pragma unroll
         for (int dx = 0; dx < N; ++dx) {
-            const float a = sa[r * VSTRIDE + c + dx], q = sc[r * VSTRIDE + c + dx], gw = g[dx];
+            const float a = sa[r * VSTRIDE + c + dx] - ca, q = sc[r * VSTRIDE + c + dx] - cq, gw = g[dx];
             rt += gw * a;
             rp += gw * q;
-            rtt += gw * a * a;
-            rpp += gw * q * q;
-            rtp += gw * a * q;
+            rtt += gw * (a * a);
+            rpp += gw * (q * q);
+            rtp += gw * (a * q);
         }
-        hq[0 * VIN * VT + k] = rt;
-        hq[1 * VIN * VT + k] = rp;
-        hq[2 * VIN * VT + k] = rtt;
-        hq[3 * VIN * VT + k] = rpp;
-        hq[4 * VIN * VT + k] = rtp;
+        hq[0 * VIN * VT + k] = ca + rt;            // row means
+        hq[1 * VIN * VT + k] = cq + rp;
+        hq[2 * VIN * VT + k] = rtt - rt * rt;      // row variances, row covariance
+        hq[3 * VIN * VT + k] = rpp - rp * rp;
+        hq[4 * VIN * VT + k] = rtp - rt * rp;
     }
     __syncthreads();
     const int ty = tid / VT, tx = tid % VT;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) m[q] = 0.f;
+    const float qt = hq[0 * VIN * VT + (ty + R) * VT + tx], qp = hq[1 * VIN * VT + (ty + R) * VT + tx];
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, b4 = 0.f, wt = 0.f, wp = 0.f, wc = 0.f;
 #pragma unroll
     for (int dy = 0; dy < N; ++dy) {
-        const float gw = g[dy];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) m[q] += gw * hq[q * VIN * VT + (ty + dy) * VT + tx];
+        const int at = (ty + dy) * VT + tx;
+        const float gw = g[dy], et = hq[0 * VIN * VT + at] - qt, ep = hq[1 * VIN * VT + at] - qp;
+        b0 += gw * et;
+        b1 += gw * ep;
+        b2 += gw * (et * et);
+        b3 += gw * (ep * ep);
+        b4 += gw * (et * ep);
+        wt += gw * hq[2 * VIN * VT + at];
+        wp += gw * hq[3 * VIN * VT + at];
+        wc += gw * hq[4 * VIN * VT + at];
     }
+    m[0] = wt + (b2 - b0 * b0);
+    m[1] = wp + (b3 - b1 * b1);
+    m[2] = wc + (b4 - b0 * b1);
 }
 
-// one window's two log10 terms from its moments m = E[t], E[p], E[tt], E[pp], E[tp] (about any origin)
-__device__ __forceinline__ void vif_terms(const float (&m)[5], double& num, double& den)
+// one window's two log10 terms from m = var t, var p, cov(t, p)
+__device__ __forceinline__ void vif_terms(const float (&m)[3], double& num, double& den)
 {
     const float eps = 1e-10f;
-    float st = m[2] - m[0] * m[0], sp = m[3] - m[1] * m[1];
+    float st = m[0], sp = m[1];
     st = st < 0.f ? 0.f : st;                  // clamp(min = 0) that keeps a NaN
     sp = sp < 0.f ? 0.f : sp;
-    const float stp = m[4] - m[0] * m[1];
+    const float stp = m[2];
     float gg = stp / (st + eps);
     float sv = sp - gg * stp;
     if (st < eps) { gg = 0.f; sv = sp; st = 0.f; }
@@ -468,7 +485,7 @@ __global__ __launch_bounds__(NT) void vif_stats_kernel(ScaleSet S, VifWeights vw
     const float* g = vif_taps_to_lds(vw, s);
     const float* t = P.y + (size_t)b * P.h * P.w;              // y = target, x = preds
     const float* p = P.x + (size_t)b * P.h * P.w;
-    float m[5];
+    float m[3];
     if (s == 0) vif_tile<17>(t, p, P.h, P.w, i0, j0, g, sa, sc, hq, m);
     else if (s == 1) vif_tile<9>(t, p, P.h, P.w, i0, j0, g, sa, sc, hq, m);
     else if (s == 2) vif_tile<5>(t, p, P.h, P.w, i0, j0, g, sa, sc, hq, m);
@@ -522,11 +539,76 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int pool2_dim(int n, int d) { return (n + d) / 2; }
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
+// ---- geometry and workspace layout of one (B, H, W): computed in one place, for xsd_ext_metrics_eval and xsd_ext_metrics_test_stage
+struct ExtLayout {
+    PoolDims pd;
+    int mk, mh, mw;                                  // MDSI: kernel size, pooled dims
+    int vh[NSCALE], vw[NSCALE];                      // VIF chain: image dims per scale ([0] = H, W)
+    int gh[NSCALE], gw[NSCALE];                      // gradient-magnitude chain: H x W, then U1..U3
+    int g_tx[NSCALE], g_nt[NSCALE], v_tx[NSCALE], v_nt[NSCALE];
+    int h_tx, h_nt, m_tx, m_nt;
+    size_t o_gms[NSCALE], o_vif[NSCALE], o_haar, o_md1, o_md2;       // doubles (tile partials) first
+    size_t o_ux, o_uy, o_mx, o_my, o_vx[NSCALE], o_vy[NSCALE];       // then the float images ([0] of o_vx / o_vy unused)
+    size_t u_off[NSCALE];                            // float offset of U1..U3 inside o_ux / o_uy ([0] unused)
+    size_t bytes;
+};
+
+ExtLayout ext_layout(int B, int H, int W)
+{
+    ExtLayout L;
+    PoolDims& pd = L.pd;
+    pd.H = H; pd.W = W;
+    int d = std::max(H % 2, W % 2);
+    pd.h1 = pool2_dim(H, d); pd.w1 = pool2_dim(W, d);
+    d = std::max(pd.h1 % 2, pd.w1 % 2);
+    pd.h2 = pool2_dim(pd.h1, d); pd.w2 = pool2_dim(pd.w1, d);
+    d = std::max(pd.h2 % 2, pd.w2 % 2);
+    pd.h3 = pool2_dim(pd.h2, d); pd.w3 = pool2_dim(pd.w2, d);
+    L.mk = std::max(1, (int)std::nearbyint((double)std::min(H, W) / 256.0));      // Python's round: ties to even
+    L.mh = (H - 1) / L.mk + 1; L.mw = (W - 1) / L.mk + 1;
+    L.vh[0] = H; L.vw[0] = W;
+    for (int s = 1; s < NSCALE; ++s) {
+        L.vh[s] = (L.vh[s - 1] - VIF_TAPS[s] + 2) / 2;
+        L.vw[s] = (L.vw[s - 1] - VIF_TAPS[s] + 2) / 2;
+    }
+    const int gh[NSCALE] = {H, pd.h1, pd.h2, pd.h3}, gw[NSCALE] = {W, pd.w1, pd.w2, pd.w3};
+
+    // ---- workspace: doubles (tile partials) first, then the float images
+    const size_t nB = (size_t)B;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    for (int s = 0; s < NSCALE; ++s) {
+        L.gh[s] = gh[s]; L.gw[s] = gw[s];
+        L.g_tx[s] = cdiv(gw[s], TW); L.g_nt[s] = L.g_tx[s] * cdiv(gh[s], TH);
+        L.v_tx[s] = cdiv(L.vw[s] - VIF_TAPS[s] + 1, VT); L.v_nt[s] = L.v_tx[s] * cdiv(L.vh[s] - VIF_TAPS[s] + 1, VT);
+        L.o_gms[s] = take(nB * L.g_nt[s] * 4 * sizeof(double));
+        L.o_vif[s] = take(nB * L.v_nt[s] * 2 * sizeof(double));
+    }
+    L.h_tx = L.g_tx[1]; L.h_nt = L.g_nt[1];
+    L.m_tx = cdiv(L.mw, TW); L.m_nt = L.m_tx * cdiv(L.mh, TH);
+    L.o_haar = take(nB * L.h_nt * 2 * sizeof(double));
+    L.o_md1 = take(nB * L.m_nt * 2 * sizeof(double));
+    L.o_md2 = take(nB * L.m_nt * sizeof(double));
+    const size_t n_u = (size_t)pd.h1 * pd.w1 + (size_t)pd.h2 * pd.w2 + (size_t)pd.h3 * pd.w3;
+    L.o_ux = take(nB * n_u * sizeof(float)); L.o_uy = take(nB * n_u * sizeof(float));
+    L.o_mx = take(nB * L.mh * L.mw * sizeof(float)); L.o_my = take(nB * L.mh * L.mw * sizeof(float));
+    L.o_vx[0] = L.o_vy[0] = 0;
+    for (int s = 1; s < NSCALE; ++s) {
+        L.o_vx[s] = take(nB * L.vh[s] * L.vw[s] * sizeof(float));
+        L.o_vy[s] = take(nB * L.vh[s] * L.vw[s] * sizeof(float));
+    }
+    L.u_off[0] = 0; L.u_off[1] = 0; L.u_off[2] = nB * pd.h1 * pd.w1;
+    L.u_off[3] = nB * ((size_t)pd.h1 * pd.w1 + (size_t)pd.h2 * pd.w2);
+    L.bytes = off;
+    return L;
+}
+
 }   // namespace
 
 struct xsd_ext_metrics {
     void* ws = nullptr;
     size_t ws_bytes = 0;
+    int B = 0, H = 0, W = 0;          // the last xsd_ext_metrics_eval that was enqueued (0: none yet)
 };
 
 int xsd_ext_metrics_create(xsd_ext_metrics** out)
@@ -560,55 +642,20 @@ int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float
                                  "needs at least 41 pixels", H, W);
     hipStream_t st = (hipStream_t)stream;
 
-    // ---- geometry
-    PoolDims pd;
-    pd.H = H; pd.W = W;
-    int d = std::max(H % 2, W % 2);
-    pd.h1 = pool2_dim(H, d); pd.w1 = pool2_dim(W, d);
-    d = std::max(pd.h1 % 2, pd.w1 % 2);
-    pd.h2 = pool2_dim(pd.h1, d); pd.w2 = pool2_dim(pd.w1, d);
-    d = std::max(pd.h2 % 2, pd.w2 % 2);
-    pd.h3 = pool2_dim(pd.h2, d); pd.w3 = pool2_dim(pd.w2, d);
-    const int mk = std::max(1, (int)std::nearbyint((double)std::min(H, W) / 256.0));      // Python's round: ties to even
-    const int mh = (H - 1) / mk + 1, mw = (W - 1) / mk + 1;
-    int vh[NSCALE] = {H, 0, 0, 0}, vw_[NSCALE] = {W, 0, 0, 0};
-    for (int s = 1; s < NSCALE; ++s) {
-        vh[s] = (vh[s - 1] - VIF_TAPS[s] + 2) / 2;
-        vw_[s] = (vw_[s - 1] - VIF_TAPS[s] + 2) / 2;
-    }
-    const int gh[NSCALE] = {H, pd.h1, pd.h2, pd.h3}, gw[NSCALE] = {W, pd.w1, pd.w2, pd.w3};
-
-    // ---- workspace: doubles (tile partials) first, then the float images
-    const size_t nB = (size_t)B;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    int g_tx[NSCALE], g_nt[NSCALE], v_tx[NSCALE], v_nt[NSCALE];
-    size_t o_gms[NSCALE], o_vif[NSCALE];
-    for (int s = 0; s < NSCALE; ++s) {
-        g_tx[s] = cdiv(gw[s], TW); g_nt[s] = g_tx[s] * cdiv(gh[s], TH);
-        v_tx[s] = cdiv(vw_[s] - VIF_TAPS[s] + 1, VT); v_nt[s] = v_tx[s] * cdiv(vh[s] - VIF_TAPS[s] + 1, VT);
-        o_gms[s] = take(nB * g_nt[s] * 4 * sizeof(double));
-        o_vif[s] = take(nB * v_nt[s] * 2 * sizeof(double));
-    }
-    const int h_tx = g_tx[1], h_nt = g_nt[1];
-    const int m_tx = cdiv(mw, TW), m_nt = m_tx * cdiv(mh, TH);
-    const size_t o_haar = take(nB * h_nt * 2 * sizeof(double));
-    const size_t o_md1 = take(nB * m_nt * 2 * sizeof(double));
-    const size_t o_md2 = take(nB * m_nt * sizeof(double));
-    const size_t n_u = (size_t)pd.h1 * pd.w1 + (size_t)pd.h2 * pd.w2 + (size_t)pd.h3 * pd.w3;
-    const size_t o_ux = take(nB * n_u * sizeof(float)), o_uy = take(nB * n_u * sizeof(float));
-    const size_t o_mx = take(nB * mh * mw * sizeof(float)), o_my = take(nB * mh * mw * sizeof(float));
-    size_t o_vx[NSCALE] = {}, o_vy[NSCALE] = {};
-    for (int s = 1; s < NSCALE; ++s) {
-        o_vx[s] = take(nB * vh[s] * vw_[s] * sizeof(float));
-        o_vy[s] = take(nB * vh[s] * vw_[s] * sizeof(float));
-    }
-    if (off > m->ws_bytes) {
+    m->B = 0;                                      // nothing to read back until this eval is enqueued whole
+    const ExtLayout L = ext_layout(B, H, W);
+    const PoolDims& pd = L.pd;
+    const int mk = L.mk, mh = L.mh, mw = L.mw, h_tx = L.h_tx, h_nt = L.h_nt, m_tx = L.m_tx, m_nt = L.m_nt;
+    const int *vh = L.vh, *vw_ = L.vw, *gh = L.gh, *gw = L.gw, *g_tx = L.g_tx, *g_nt = L.g_nt, *v_tx = L.v_tx, *v_nt = L.v_nt;
+    const size_t *o_gms = L.o_gms, *o_vif = L.o_vif, *o_vx = L.o_vx, *o_vy = L.o_vy, *u_off = L.u_off;
+    const size_t o_haar = L.o_haar, o_md1 = L.o_md1, o_md2 = L.o_md2, o_ux = L.o_ux, o_uy = L.o_uy, o_mx = L.o_mx, o_my = L.o_my;
+    if (L.bytes > m->ws_bytes) {
         EXTM_HIPCHK(hipStreamSynchronize(st));
         if (m->ws) EXTM_HIPCHK(hipFree(m->ws));
-        m->ws = nullptr; m->ws_bytes = 0;
-        if (hipMalloc(&m->ws, off) != hipSuccess) return fail(XSD_ERR_NOMEM, "xsd_ext_metrics_eval: workspace allocation of %zu bytes failed", off);
-        m->ws_bytes = off;
+        m->ws = nullptr; m->ws_bytes = 0; m->B = 0;
+        if (hipMalloc(&m->ws, L.bytes) != hipSuccess)
+            return fail(XSD_ERR_NOMEM, "xsd_ext_metrics_eval: workspace allocation of %zu bytes failed", L.bytes);
+        m->ws_bytes = L.bytes;
     }
     char* ws = (char*)m->ws;
     auto F = [&](size_t o) { return (float*)(ws + o); };
@@ -643,7 +690,6 @@ int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float
     // 6: gradient magnitude similarity, four scales
     ScaleSet G, V;
     int g_max = 0, v_max = 0;
-    const size_t u_off[NSCALE] = {0, 0, nB * pd.h1 * pd.w1, nB * ((size_t)pd.h1 * pd.w1 + (size_t)pd.h2 * pd.w2)};
     for (int s = 0; s < NSCALE; ++s) {
         G.p[s].x = s == 0 ? dev_preds : F(o_ux) + u_off[s];
         G.p[s].y = s == 0 ? dev_target : F(o_uy) + u_off[s];
@@ -678,5 +724,50 @@ int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float
     A.mdsi_count = (double)mh * (double)mw;
     hipLaunchKernelGGL(finish_kernel, dim3(B), blk, 0, st, A, dev_out);
     EXTM_HIPCHK(hipGetLastError());
+    m->B = B; m->H = H; m->W = W;
+    return XSD_OK;
+}
+
+int xsd_ext_metrics_test_stage(xsd_ext_metrics* m, int stage, int side, void* dev_dst, int64_t dst_bytes, int* info, void* stream)
+{
+    if (!m || !dev_dst || !info) return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: null pointer");
+    if (stage < 0 || stage >= XSD_EXTM_STAGES) return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: unknown stage %d (0..%d)", stage, XSD_EXTM_STAGES - 1);
+    if (side != 0 && side != 1) return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: side must be 0 (preds) or 1 (target), got %d", side);
+    if (!m->B || !m->ws) return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: this handle has not evaluated anything yet");
+    const ExtLayout L = ext_layout(m->B, m->H, m->W);
+    const size_t nB = (size_t)m->B;
+    size_t off = 0, bytes = 0;
+    int h = 0, w = 0, entries = 0, tx = 0, nt = 0, th = TH, tw = TW;
+    if (stage <= XSD_EXTM_STAGE_U3) {                        // U1..U3
+        const int s = stage - XSD_EXTM_STAGE_U1 + 1;
+        h = L.gh[s]; w = L.gw[s];
+        off = (side ? L.o_uy : L.o_ux) + L.u_off[s] * sizeof(float);
+    } else if (stage == XSD_EXTM_STAGE_M) {
+        h = L.mh; w = L.mw;
+        off = side ? L.o_my : L.o_mx;
+    } else if (stage <= XSD_EXTM_STAGE_V3) {                 // V1..V3
+        const int s = stage - XSD_EXTM_STAGE_V1 + 1;
+        h = L.vh[s]; w = L.vw[s];
+        off = side ? L.o_vy[s] : L.o_vx[s];
+    } else if (stage <= XSD_EXTM_STAGE_GMS3) {
+        const int s = stage - XSD_EXTM_STAGE_GMS0;
+        h = L.gh[s]; w = L.gw[s]; entries = 4; tx = L.g_tx[s]; nt = L.g_nt[s]; off = L.o_gms[s];
+    } else if (stage == XSD_EXTM_STAGE_HAAR) {
+        h = L.gh[1]; w = L.gw[1]; entries = 2; tx = L.h_tx; nt = L.h_nt; off = L.o_haar;
+    } else if (stage == XSD_EXTM_STAGE_MDSI1 || stage == XSD_EXTM_STAGE_MDSI2) {
+        const bool first = stage == XSD_EXTM_STAGE_MDSI1;
+        h = L.mh; w = L.mw; entries = first ? 2 : 1; tx = L.m_tx; nt = L.m_nt; off = first ? L.o_md1 : L.o_md2;
+    } else {
+        const int s = stage - XSD_EXTM_STAGE_VIF0;
+        h = L.vh[s] - VIF_TAPS[s] + 1; w = L.vw[s] - VIF_TAPS[s] + 1;       // windows, not pixels
+        entries = 2; tx = L.v_tx[s]; nt = L.v_nt[s]; off = L.o_vif[s]; th = VT; tw = VT;
+    }
+    bytes = entries ? nB * nt * entries * sizeof(double) : nB * h * w * sizeof(float);
+    info[0] = m->B; info[1] = h; info[2] = w; info[3] = entries;
+    info[4] = entries ? tx : 0; info[5] = entries ? nt : 0; info[6] = entries ? th : 0; info[7] = entries ? tw : 0;
+    if (dst_bytes < 0 || (size_t)dst_bytes < bytes)
+        return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: buffer too small for stage %d: %lld bytes given, %zu needed", stage, (long long)dst_bytes, bytes);
+    if (off + bytes > m->ws_bytes) return fail(XSD_ERR_ARG, "xsd_ext_metrics_test_stage: the region lies outside the workspace");
+    EXTM_HIPCHK(hipMemcpyAsync(dev_dst, (const char*)m->ws + off, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return XSD_OK;
 }

@@ -450,6 +450,7 @@ struct xsd_fsim {
     size_t ws_bytes = 0;
     Plan plans[XSD_FSIM_PLANS];
     unsigned long long clock = 0;
+    int B = 0, h = 0, w = 0;          // the last xsd_fsim_eval that was enqueued: batch and pooled size (0: none yet)
 };
 
 #define FSIM_HIPCHK(expr)                                                                                                      \
@@ -520,6 +521,35 @@ void cgemm(hipStream_t st, const Opnd& A, const Opnd& B, void* C, int c_f32, dou
     hipLaunchKernelGGL(cgemm_kernel, dim3(cdiv(N, GN), cdiv(M, GM), batch), dim3(256), 0, st, A, B, C, c_f32, scale, M, N, K);
 }
 
+// workspace layout of one (B, h, w): computed in one place, for xsd_fsim_eval and xsd_fsim_test_stage
+struct FsimLayout {
+    size_t hw, S2;
+    int tiles_x, ntiles;
+    size_t o_pool, o_y, o_f, o_z, o_eo, o_en, o_an, o_a0, o_T, o_part, bytes;
+};
+
+FsimLayout fsim_layout(int B, int h, int w)
+{
+    FsimLayout L;
+    const size_t hw = (size_t)h * w, S2 = 2 * (size_t)B;
+    L.hw = hw; L.S2 = S2;
+    L.tiles_x = cdiv(w, TW); L.ntiles = L.tiles_x * cdiv(h, TH);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
+    L.o_pool = take(S2 * hw * sizeof(double));
+    L.o_y = take(S2 * hw * sizeof(double2));
+    L.o_f = take(S2 * hw * sizeof(double2));
+    L.o_z = take(S2 * NF * hw * sizeof(double2));
+    L.o_eo = take(S2 * NF * hw * sizeof(float2));
+    L.o_en = take(S2 * NO * hw * sizeof(double));
+    L.o_an = take(S2 * NO * hw * sizeof(double));
+    L.o_a0 = take(S2 * NO * hw * sizeof(float));
+    L.o_T = take(S2 * NO * sizeof(double));
+    L.o_part = take((size_t)B * L.ntiles * 2 * sizeof(double));
+    L.bytes = off;
+    return L;
+}
+
 }   // namespace
 
 int xsd_fsim_create(xsd_fsim** out)
@@ -555,28 +585,18 @@ int xsd_fsim_eval(xsd_fsim* m, const float* dev_preds, const float* dev_target, 
     int rc = get_plan(m, h, w, st, &P);
     if (rc != XSD_OK) return rc;
 
-    const size_t hw = (size_t)h * w, S2 = 2 * (size_t)B;
-    const int tiles_x = cdiv(w, TW), ntiles = tiles_x * cdiv(h, TH);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-    const size_t o_pool = take(S2 * hw * sizeof(double));
-    const size_t o_y = take(S2 * hw * sizeof(double2));
-    const size_t o_f = take(S2 * hw * sizeof(double2));
-    const size_t o_z = take(S2 * NF * hw * sizeof(double2));
-    const size_t o_eo = take(S2 * NF * hw * sizeof(float2));
-    const size_t o_en = take(S2 * NO * hw * sizeof(double));
-    const size_t o_an = take(S2 * NO * hw * sizeof(double));
-    const size_t o_a0 = take(S2 * NO * hw * sizeof(float));
-    const size_t o_T = take(S2 * NO * sizeof(double));
-    const size_t o_part = take((size_t)B * ntiles * 2 * sizeof(double));
-    rc = reserve(m, off, st, "xsd_fsim_eval");
+    const FsimLayout L = fsim_layout(B, h, w);
+    const size_t hw = L.hw, S2 = L.S2;
+    const int tiles_x = L.tiles_x, ntiles = L.ntiles;
+    m->B = 0;                                      // nothing to read back until this eval is enqueued whole
+    rc = reserve(m, L.bytes, st, "xsd_fsim_eval");
     if (rc != XSD_OK) return rc;
     char* ws = (char*)m->ws;
-    double* pooled = (double*)(ws + o_pool);
-    double2 *Y = (double2*)(ws + o_y), *F = (double2*)(ws + o_f), *Z = (double2*)(ws + o_z);
-    float2* EO = (float2*)(ws + o_eo);
-    double *EN = (double*)(ws + o_en), *AN = (double*)(ws + o_an), *T = (double*)(ws + o_T), *part = (double*)(ws + o_part);
-    float* A0 = (float*)(ws + o_a0);
+    double* pooled = (double*)(ws + L.o_pool);
+    double2 *Y = (double2*)(ws + L.o_y), *F = (double2*)(ws + L.o_f), *Z = (double2*)(ws + L.o_z);
+    float2* EO = (float2*)(ws + L.o_eo);
+    double *EN = (double*)(ws + L.o_en), *AN = (double*)(ws + L.o_an), *T = (double*)(ws + L.o_T), *part = (double*)(ws + L.o_part);
+    float* A0 = (float*)(ws + L.o_a0);
 
     const dim3 blk(TW, TH);
     // 1
@@ -599,6 +619,47 @@ int xsd_fsim_eval(xsd_fsim* m, const float* dev_preds, const float* dev_target, 
     // 9
     hipLaunchKernelGGL(fsim_finish_kernel, dim3(B), blk, 0, st, (const double*)part, dev_out, ntiles);
     FSIM_HIPCHK(hipGetLastError());
+    m->B = B; m->h = h; m->w = w;
+    return XSD_OK;
+}
+
+int xsd_fsim_test_stage(xsd_fsim* m, int stage, void* dev_dst, int64_t dst_bytes, int* info, void* stream)
+{
+    if (!m || !dev_dst || !info) return fail(XSD_ERR_ARG, "xsd_fsim_test_stage: null pointer");
+    if (stage < 0 || stage >= XSD_FSIM_STAGES) return fail(XSD_ERR_ARG, "xsd_fsim_test_stage: unknown stage %d (0..%d)", stage, XSD_FSIM_STAGES - 1);
+    const Plan* P = nullptr;
+    if (m->B)
+        for (const Plan& p : m->plans)
+            if (p.h == m->h && p.w == m->w) P = &p;
+    if (!m->B || !m->ws || !P) return fail(XSD_ERR_ARG, "xsd_fsim_test_stage: this handle has not evaluated anything yet (or its plan is gone)");
+    const FsimLayout L = fsim_layout(m->B, m->h, m->w);
+    const size_t hw = L.hw, S2 = L.S2;
+    size_t off = 0, bytes = 0;
+    int lead = (int)S2;
+    const void* src = nullptr;                                 // outside the workspace: the plan
+    hipMemcpyKind kind = hipMemcpyDeviceToDevice;
+    switch (stage) {
+    case XSD_FSIM_STAGE_POOLED: off = L.o_pool; bytes = S2 * hw * sizeof(double); break;
+    case XSD_FSIM_STAGE_EO: off = L.o_eo; bytes = S2 * NF * hw * sizeof(float2); break;
+    case XSD_FSIM_STAGE_EN: off = L.o_en; bytes = S2 * NO * hw * sizeof(double); break;
+    case XSD_FSIM_STAGE_AN: off = L.o_an; bytes = S2 * NO * hw * sizeof(double); break;
+    case XSD_FSIM_STAGE_A0SQ: off = L.o_a0; bytes = S2 * NO * hw * sizeof(float); break;
+    case XSD_FSIM_STAGE_T: off = L.o_T; bytes = S2 * NO * sizeof(double); break;
+    case XSD_FSIM_STAGE_PART: off = L.o_part; bytes = (size_t)m->B * L.ntiles * 2 * sizeof(double); lead = m->B; break;
+    case XSD_FSIM_STAGE_FILT: src = P->filt; bytes = (size_t)NF * hw * sizeof(double); lead = NF; break;
+    default: src = &P->nc; bytes = sizeof(NoiseConsts); lead = 3; kind = hipMemcpyHostToDevice; break;
+    }
+    const bool part = stage == XSD_FSIM_STAGE_PART;
+    info[0] = lead; info[1] = m->h; info[2] = m->w; info[3] = part ? 2 : 0;
+    info[4] = part ? L.tiles_x : 0; info[5] = part ? L.ntiles : 0; info[6] = part ? TH : 0; info[7] = part ? TW : 0;
+    if (dst_bytes < 0 || (size_t)dst_bytes < bytes)
+        return fail(XSD_ERR_ARG, "xsd_fsim_test_stage: buffer too small for stage %d: %lld bytes given, %zu needed", stage, (long long)dst_bytes, bytes);
+    if (!src) {
+        if (off + bytes > m->ws_bytes) return fail(XSD_ERR_ARG, "xsd_fsim_test_stage: the region lies outside the workspace");
+        src = (const char*)m->ws + off;
+    }
+    if (kind == hipMemcpyHostToDevice) FSIM_HIPCHK(hipMemcpy(dev_dst, src, bytes, kind));      // 96 bytes of pageable host memory
+    else FSIM_HIPCHK(hipMemcpyAsync(dev_dst, src, bytes, kind, (hipStream_t)stream));
     return XSD_OK;
 }
 
@@ -615,6 +676,7 @@ int xsd_fsim_test_dft2(xsd_fsim* m, const float* dev_in, float* dev_out, int B, 
     const size_t n = (size_t)n1 * n2;
     rc = reserve(m, align256((size_t)B * n * sizeof(double2)), st, "xsd_fsim_test_dft2");
     if (rc != XSD_OK) return rc;
+    m->B = 0;                                      // the transform's scratch overwrites the last eval's regions
     double2* tmp = (double2*)m->ws;
     if (!inverse) {
         cgemm(st, opnd(dev_in, K_CF32, 0, n2, (long long)n), opnd(P->Ww, K_CF64, 0, n2, 0), tmp, 0, 1.0, n1, n2, n2, B);

@@ -729,6 +729,34 @@ def restormer_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | Non
     return out
 
 
+def _copy_stage(call, out, device, layout):
+    """shared by ExtMetricsEngine.stage and FsimEngine.stage: `call(ptr, nbytes, info)` is the C hook, which fills `info` before it
+    judges the buffer; without `out` a first call with an 8-byte buffer learns the region's dims (a region that small is simply
+    copied), a second one copies into a tensor of the right size.  layout(info) -> (dtype, shape)."""
+    info = (ctypes.c_int32 * 8)()
+    if out is None:
+        probe = torch.empty(8, device=device, dtype=torch.uint8)
+        rc = call(probe.data_ptr(), 8, info)
+        if rc != 0 and b"buffer too small" not in _lib.load().xsd_last_error():
+            check(rc)
+        dtype, shape = layout(info)
+        out = torch.empty(shape, device=device, dtype=dtype)
+        check(call(out.data_ptr(), out.numel() * out.element_size(), info))
+    else:
+        if not out.is_cuda or not out.is_contiguous():
+            raise XsdError("out must be a contiguous device tensor")
+        check(call(out.data_ptr(), out.numel() * out.element_size(), info))
+        dtype, shape = layout(info)
+        if out.dtype != dtype:
+            raise XsdError(f"out is {out.dtype}, the region is {dtype}")
+        n = 1
+        for k in shape:
+            n *= k
+        out = out.reshape(-1)[:n].reshape(shape)
+    keys = ("B", "h", "w", "entries", "tiles_x", "ntiles", "tile_h", "tile_w")
+    return out, dict(zip(keys, (int(v) for v in info)))
+
+
 class ExtMetricsEngine:
     """The extended test metrics of one batch (include/xsd.h: xsd_ext_metrics_eval): gmsd, ms_gmsd, haarpsi, mdsi and the two
     VIF sums per image, as doubles.  The formulas restate piq 0.7.x / torchmetrics 1.x from their published code; parity with
@@ -768,6 +796,22 @@ class ExtMetricsEngine:
         out = torch.empty((B, self.OUT), device=preds.device, dtype=torch.float64)
         check(self.L.xsd_ext_metrics_eval(self.h, preds.data_ptr(), target.data_ptr(), out.data_ptr(), B, H, W, _stream_ptr(preds.device)))
         return out
+
+    # the regions xsd_ext_metrics_test_stage copies out (include/xsd.h: XSD_EXTM_STAGE_*)
+    STAGES = ("u1", "u2", "u3", "m", "v1", "v2", "v3", "gms0", "gms1", "gms2", "gms3", "haar", "mdsi1", "mdsi2", "vif0", "vif1", "vif2", "vif3")
+
+    @_on_engine_device
+    def stage(self, name: str, side: int = 0, out: torch.Tensor | None = None):
+        """One region of the last eval's workspace (include/xsd.h: xsd_ext_metrics_test_stage) -> (tensor, info).  An image
+        ("u1".."u3", "m", "v1".."v3"; side 0 = preds, 1 = target) is fp32 [B, h, w]; tile partials ("gms0".."gms3", "haar", "mdsi1",
+        "mdsi2", "vif0".."vif3") are float64 [B, ntiles, entries].  info: dict(B, h, w, entries, tiles_x, ntiles, tile_h, tile_w).  The
+        copy goes into `out` (a contiguous device tensor of the region's dtype and at least its size, reshaped) if given."""
+        if name not in self.STAGES:
+            raise XsdError(f"unknown stage {name!r} (one of {self.STAGES})")
+        return _copy_stage(lambda ptr, nbytes, info: self.L.xsd_ext_metrics_test_stage(self.h, self.STAGES.index(name), int(side), ptr, nbytes, info,
+                                                                                       _stream_ptr(torch.device("cuda", self.device_index))),
+                           out, torch.device("cuda", self.device_index),
+                           lambda i: (torch.float64, (i[0], i[5], i[3])) if i[3] else (torch.float32, (i[0], i[1], i[2])))
 
 
 class FsimEngine:
@@ -822,6 +866,28 @@ class FsimEngine:
         B, n1, n2, _ = x.shape
         check(self.L.xsd_fsim_test_dft2(self.h, x.data_ptr(), out.data_ptr(), B, n1, n2, int(bool(inverse)), _stream_ptr(x.device)))
         return out
+
+    # the regions xsd_fsim_test_stage copies out (include/xsd.h: XSD_FSIM_STAGE_*)
+    STAGES = ("pooled", "eo", "en", "an", "a0sq", "T", "part", "filt", "noise")
+
+    @_on_engine_device
+    def stage(self, name: str, out: torch.Tensor | None = None):
+        """One region of the last eval's workspace or plan (include/xsd.h: xsd_fsim_test_stage) -> (tensor, info): "pooled" float64
+        [2B, h, w]; "eo" fp32 [2B, 16, h, w, 2]; "en", "an" float64 and "a0sq" fp32 [2B, 4, h, w]; "T" float64 [2B, 4]; "part" float64
+        [B, ntiles, 2]; "filt" float64 [16, h, w]; "noise" float64 [3, 4].  info: dict(B = the leading count, h, w, entries, tiles_x,
+        ntiles, tile_h, tile_w).  The copy goes into `out` (a contiguous device tensor of the region's dtype, at least its size) if given."""
+        if name not in self.STAGES:
+            raise XsdError(f"unknown stage {name!r} (one of {self.STAGES})")
+        f32, f64 = torch.float32, torch.float64
+
+        def layout(i):
+            n, h, w = i[0], i[1], i[2]
+            return {"pooled": (f64, (n, h, w)), "eo": (f32, (n, 16, h, w, 2)), "en": (f64, (n, 4, h, w)), "an": (f64, (n, 4, h, w)),
+                    "a0sq": (f32, (n, 4, h, w)), "T": (f64, (n, 4)), "part": (f64, (n, i[5], 2)), "filt": (f64, (16, h, w)),
+                    "noise": (f64, (3, 4))}[name]
+        dev = torch.device("cuda", self.device_index)
+        return _copy_stage(lambda ptr, nbytes, info: self.L.xsd_fsim_test_stage(self.h, self.STAGES.index(name), ptr, nbytes, info, _stream_ptr(dev)),
+                           out, dev, layout)
 
 
 @_on_tensor_device
