@@ -408,6 +408,41 @@ int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, i
  * the stream. */
 int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int conv3, int B, int H, int W, int cin,
                      int N, int64_t ldy, int act, float slope, int math, void* stream);
+/* One launch of the same GEMM described as the forwards describe theirs (tests): the views, the residual and the store modes that
+ * xsd_sw_test_gemm leaves out.  Every pointer is a device pointer.  The call packs the weights itself, fills the kernel's parameters
+ * through the helpers the forwards use plus the field assignments they make, launches in `math` and synchronises the stream.  The
+ * caller sizes the buffers; an inconsistent description is refused with XSD_ERR_ARG and a message that names the field. */
+typedef struct xsd_sw_gemm_view {
+    int32_t conv3;                 /* 0: token rows, M = B H W of them; 1: 3x3 conv (zero padding 1) over B images of H x W */
+    int32_t B, H, W, cin, N;
+    const float* a;                /* token-major rows of pitch lda >= cin floats (conv3: lda = cin), or with a_nchw (conv3 only) [B][cin][H][W] */
+    int32_t a_nchw;
+    int64_t lda;
+    const float* imean;            /* conv3 only, [cin] or NULL: the conv reads (x - imean[ci]) * irange inside the image, 0 outside */
+    float irange;
+    const float* w;                /* [N][cin] (Linear) or [N][cin][3][3] (Conv2d) */
+    const float* bias;             /* [N] or NULL */
+    int32_t act;                   /* 0 none, 1 GELU (exact erf), 2 LeakyReLU(slope) */
+    float slope;
+    const float* res;              /* NULL, or + res[b rbs + p rps + n] after the activation (image b, row p of it, column n); may be y itself.
+                                    * Token rows are one image: rbs must be 0 there. */
+    int64_t rbs, rps;
+    int32_t omode;                 /* 0 token-major y[row ldy + n], ldy >= N; 1 PixelShuffle(r) into the token-major r H x r W image of N / r^2
+                                    * channels (conv3 only); 2 NCHW [B][N][H][W] = v / orange + omean[n] (conv3 only); 3 see below */
+    float* y;
+    int64_t ldy;
+    int32_t r;
+    const float* omean;            /* [N] (omode 2) or [N / r^2] (omode 3) */
+    float orange;
+    int32_t math;                  /* 0 fp32, 3 bf16x6 */
+    /* xsd_swinir_test_gemm_view only; xsd_sw_test_gemm_view refuses a non-zero value in any of them */
+    int32_t rnchw;                 /* the residual is NCHW: res[b rbs + n H W + p] */
+    int32_t cH, cW;                /* omode 2: store only rows < cH and columns < cW, as [B][N][cH][cW] (both 0: no crop).  omode 3: PixelShuffle(r)
+                                    * of the N columns, v / orange + omean[ch], into [B][N / r^2][cH][cW], the crop of r H x r W (both required) */
+    int32_t up2;                   /* conv3 only: the conv runs over the nearest-2x upsampling of the H x W input, which is never made: 4 B H W
+                                    * output rows, and H and W of the residual, the store and the crop are 2 H and 2 W */
+} xsd_sw_gemm_view;
+int xsd_sw_test_gemm_view(const xsd_sw_gemm_view* view, void* stream);
 /* The shifted-window attention that SwinFIR and HAT share, on its own (tests; modules.py:115-140 between the qkv Linear and proj, with the
  * roll, window partition and reverse of :316-340): qkv [B][H W][3 C] token rows in image order (q, k, v; head h at channels h hd .. of
  * each), table [(2 ws - 1)^2][heads] the relative-position bias -> out [B][H W][C] in image order.  With shift > 0 the windows are
@@ -550,6 +585,9 @@ int xsd_swinir_test_pad(const float* dev_x, float* dev_y, int B, int C, int H, i
  * the upsampled image is never stored.  math 0 (fp32) or 3 (bf16x6).  Synchronises the stream. */
 int xsd_swinir_test_nearest_conv(const float* dev_a, const float* dev_w, const float* dev_bias, float* dev_y, int B, int H, int W, int cin, int N,
                                  float slope, int math, void* stream);
+/* xsd_sw_test_gemm_view on SwinIR's instance of the GEMM, which takes the last four fields of the view too and adds the bias inside its
+ * double sum (one rounding to fp32). */
+int xsd_swinir_test_gemm_view(const xsd_sw_gemm_view* view, void* stream);
 
 /* ---- differentiable Swin ops (csrc/sw_ops.hip) ----------------------------------------------------------------
  * The four operations of the Swin-family engines (the GEMM as a Linear and as a 3x3 conv, the token LayerNorm, the shifted-window

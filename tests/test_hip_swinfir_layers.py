@@ -24,12 +24,22 @@ def _errs(y, ref):
     ("sfb_3_layers_qk_scale", dict(BASE, depths=[2, 2, 1], num_heads=[2, 2, 2], qk_scale=0.3)),
 ])
 def test_several_layers_match_float64_restatement(name, cfg):
+    _run(name, cfg, (2, 1, 16, 24))
+
+
+@pytest.mark.gpu
+def test_sfb_at_14_x_22_runs_the_radix_7_and_11_passes():
+    """the FourierUnit at H = 2 x 7 and W = 2 x 11 inside the network: window 2, SFB, two layers"""
+    _run("sfb_14x22_window_2", dict(BASE, img_size=14, window_size=2, depths=[2, 1], num_heads=[2, 2]), (2, 1, 14, 22))
+
+
+def _run(name, cfg, shape):
     from xmm_superres_denoise.models import SwinFIR
     state = gs.make_state(cfg, 41)
     m = SwinFIR(**gs.full_cfg(**cfg))
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in state.items()})
     m = m.cuda()
-    x = torch.from_numpy(gs.make_input((2, 1, 16, 24), 42)).cuda()
+    x = torch.from_numpy(gs.make_input(shape, 42)).cuda()
     with torch.no_grad():
         y = m(x)
         y64 = st.swinfir_forward({k: torch.from_numpy(v).cuda().double() if v.dtype == np.float32 else torch.from_numpy(v).cuda()

@@ -128,7 +128,7 @@ def test_out_size_rule_and_binding():
     from xmm_superres_denoise.engine import XsdError, _lib
     L = _lib.load()
     assert L.xsd_swinir_out_size.argtypes[1:3] == [ctypes.c_int, ctypes.c_int] and len(L.xsd_swinir_out_size.argtypes) == 5
-    for s in ("create", "destroy", "param_count", "pack_weights", "forward", "out_size", "set_math", "get_math", "test_pad", "test_nearest_conv"):
+    for s in ("create", "destroy", "param_count", "pack_weights", "forward", "out_size", "set_math", "get_math", "test_pad", "test_nearest_conv", "test_gemm_view"):
         assert "xsd_swinir_" + s in _lib.ABI_SYMBOLS and hasattr(L, "xsd_swinir_" + s)
     for case, spec in gi.CASES.items():
         m = _swinir(**gi.full_cfg(**spec["cfg"]))
@@ -163,7 +163,7 @@ def test_header_declares_the_swinir_entry_points():
     hdr = open(os.path.join(ROOT, "include", "xsd.h")).read()
     declared = set(re.findall(r"\b(xsd_swinir_[a-z0-9_]+)\s*\(", hdr))
     assert declared == {"xsd_swinir_" + s for s in ("create", "destroy", "param_count", "pack_weights", "forward", "out_size", "set_math",
-                                                    "get_math", "test_pad", "test_nearest_conv")}
+                                                    "get_math", "test_pad", "test_nearest_conv", "test_gemm_view")}
     assert "typedef struct xsd_swinir_config" in hdr and "swinir.py:350-395" in hdr
 
 

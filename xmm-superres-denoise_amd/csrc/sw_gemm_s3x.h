@@ -359,6 +359,103 @@ int test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, flo
     return XSD_OK;
 }
 
+// One launch described as the forwards describe theirs (tests): see include/xsd.h, xsd_sw_gemm_view.  GemmP comes from gp_tok / gp_conv /
+// gp_conv_up2 plus the field assignments of head(), tail(), the SFB tail, out_nchw() and the SwinIR heads; the launch is theirs too.
+// Host code only.  A file built without SW_GEMM_EXT refuses the fields its kernels do not read.
+int test_gemm_view(const xsd_sw_gemm_view* v, hipStream_t s)
+{
+    if (!v) return rfail(XSD_ERR_ARG, "GEMM view test: the view is null");
+    if (!v->a) return rfail(XSD_ERR_ARG, "GEMM view test: a is null");
+    if (!v->w) return rfail(XSD_ERR_ARG, "GEMM view test: w is null");
+    if (!v->y) return rfail(XSD_ERR_ARG, "GEMM view test: y is null");
+    const bool conv = v->conv3 != 0, up2 = v->up2 != 0;
+    const int B = v->B, H = v->H, W = v->W, cin = v->cin, N = v->N;
+    if (B < 1 || H < 1 || W < 1 || cin < 1 || N < 1 || cin > 65536 || N > 65536 || H > (1 << 14) || W > (1 << 14))
+        return rfail(XSD_ERR_ARG, "GEMM view test: bad shape B %d, H %d, W %d, cin %d, N %d", B, H, W, cin, N);
+#if !SW_GEMM_EXT
+    if (v->rnchw || v->cH || v->cW || v->up2 || v->omode == O_SHUFFLE_NCHW)
+        return rfail(XSD_ERR_ARG, "GEMM view test: rnchw, cH, cW, up2 and omode 3 belong to xsd_swinir_test_gemm_view (this instance of the "
+                     "kernel is built without them)");
+#endif
+    const int oH = up2 ? 2 * H : H, oW = up2 ? 2 * W : W;
+    const long long rows = (long long)B * oH * oW;
+    if (rows > (1ll << 28)) return rfail(XSD_ERR_ARG, "GEMM view test: %lld rows are too many", rows);
+    if (v->act < ACT_NONE || v->act > ACT_LRELU) return rfail(XSD_ERR_ARG, "GEMM view test: act %d (0 none, 1 GELU, 2 LeakyReLU)", v->act);
+    if (v->math != 0 && v->math != 3) return rfail(XSD_ERR_ARG, "GEMM view test: math %d; the math modes are fp32 (0) and bf16x6 (3)", v->math);
+    if (!conv && (v->a_nchw || v->imean || up2 || v->rnchw || v->omode != O_TOK))
+        return rfail(XSD_ERR_ARG, "GEMM view test: a_nchw, imean, up2, rnchw and omode %d need conv3 (token rows have no image)", v->omode);
+    if (v->a_nchw && up2) return rfail(XSD_ERR_ARG, "GEMM view test: a_nchw with up2 is a form no forward launches");
+    if (!v->a_nchw && (conv ? v->lda != cin : v->lda < cin))
+        return rfail(XSD_ERR_ARG, "GEMM view test: lda %lld (token rows: at least cin = %d; conv3: exactly cin)", (long long)v->lda, cin);
+    if (v->res && !conv && v->rbs != 0) return rfail(XSD_ERR_ARG, "GEMM view test: rbs %lld on token rows, which are one image", (long long)v->rbs);
+    if (v->res && (v->rbs < 0 || v->rps < 0)) return rfail(XSD_ERR_ARG, "GEMM view test: negative rbs or rps");
+    if (v->cH < 0 || v->cW < 0 || (v->cH == 0) != (v->cW == 0)) return rfail(XSD_ERR_ARG, "GEMM view test: cH %d and cW %d (both or neither)", v->cH, v->cW);
+    const int r = v->r;
+    switch (v->omode) {
+    case O_TOK:
+        if (v->ldy < N) return rfail(XSD_ERR_ARG, "GEMM view test: ldy %lld is less than N = %d", (long long)v->ldy, N);
+        if (v->cH) return rfail(XSD_ERR_ARG, "GEMM view test: cH and cW go with omode 2 or 3");
+        break;
+    case O_SHUFFLE:
+    case O_SHUFFLE_NCHW:
+        if (r < 1 || r > 8 || N % (r * r)) return rfail(XSD_ERR_ARG, "GEMM view test: N = %d is no multiple of r^2 (r = %d, 1..8)", N, r);
+        if (v->omode == O_SHUFFLE && v->cH) return rfail(XSD_ERR_ARG, "GEMM view test: cH and cW go with omode 2 or 3");
+        if (v->omode == O_SHUFFLE_NCHW && !v->cH) return rfail(XSD_ERR_ARG, "GEMM view test: omode 3 needs cH and cW");
+        if (v->cH > r * oH || v->cW > r * oW)
+            return rfail(XSD_ERR_ARG, "GEMM view test: the crop cH %d x cW %d is larger than the %d x %d result", v->cH, v->cW, r * oH, r * oW);
+        break;
+    case O_NCHW:
+        if (v->cH > oH || v->cW > oW)
+            return rfail(XSD_ERR_ARG, "GEMM view test: the crop cH %d x cW %d is larger than the %d x %d result", v->cH, v->cW, oH, oW);
+        break;
+    default:
+        return rfail(XSD_ERR_ARG, "GEMM view test: omode %d (0 token-major, 1 PixelShuffle, 2 NCHW, 3 PixelShuffle into NCHW)", v->omode);
+    }
+    if (v->omode == O_NCHW || v->omode == O_SHUFFLE_NCHW) {
+        if (!v->omean) return rfail(XSD_ERR_ARG, "GEMM view test: omean is null");
+        if (!(v->orange > 0)) return rfail(XSD_ERR_ARG, "GEMM view test: orange must be positive");
+    }
+    const int taps = conv ? 9 : 1, K = cin * taps;
+    const long long wn = (long long)N * K;
+    const size_t bytes = v->math == 3 ? sizeof(unsigned short) * (size_t)(3 * sx_plane_elems(N, K)) : sizeof(float) * (size_t)wn;
+    void* wp = nullptr;
+    if (hipMalloc(&wp, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return rfail(XSD_ERR_NOMEM, "GEMM view test: allocation failed");
+    }
+    hipError_t e;
+    if (v->math == 3) {
+        e = pack_s3x(s, v->w, (unsigned short*)wp, N, cin, taps);
+    } else {
+        hipLaunchKernelGGL(sw_pack_kernel, dim3((unsigned)((wn + 255) / 256)), dim3(256), 0, s, v->w, (float*)wp, N, cin, taps);
+        e = hipGetLastError();
+    }
+    if (!e) {
+        const long long ldy = v->omode == O_TOK ? v->ldy : 0, oHW = (long long)oH * oW;
+        GemmP p = up2    ? gp_conv_up2(v->a, B, H, W, cin, (const float*)wp, N, v->bias, v->y, ldy)
+                  : conv ? gp_conv(v->a, B, H, W, cin, (const float*)wp, N, v->bias, v->y, ldy)
+                         : gp_tok(v->a, rows, cin, v->lda, (const float*)wp, N, v->bias, v->y, ldy);
+        if (v->a_nchw) { p.acs = (long long)H * W; p.aps = 1; }                      // head()
+        if (v->imean) { p.isub = v->imean; p.imul = v->irange; }
+        p.act = v->act; p.slope = v->slope;
+        if (v->res) { p.res = v->res; p.rbs = v->rbs; p.rps = v->rps; p.rnchw = v->rnchw; }
+        if (v->omode == O_SHUFFLE) {                                                  // tail()
+            p.omode = O_SHUFFLE; p.r = r; p.ybs = oHW * N; p.yps = N / (r * r);
+        } else if (v->omode == O_NCHW) {                                              // tail(), out_nchw()
+            p.omode = O_NCHW; p.ybs = N * oHW; p.omean = v->omean; p.orange = v->orange;
+            if (v->cW) { p.cH = v->cH; p.cW = v->cW; p.ybs = (long long)N * v->cH * v->cW; }
+        } else if (v->omode == O_SHUFFLE_NCHW) {                                      // UpsampleOneStep in swinir.hip
+            p.omode = O_SHUFFLE_NCHW; p.r = r; p.cH = v->cH; p.cW = v->cW; p.ybs = (long long)(N / (r * r)) * v->cH * v->cW;
+            p.omean = v->omean; p.orange = v->orange;
+        }
+        e = v->math == 3 ? gemm_s3x(s, p, (const unsigned short*)wp) : gemm(s, p);
+    }
+    hipStreamSynchronize(s);
+    hipFree(wp);
+    if (e) return rfail(XSD_ERR_HIP, "GEMM view test: %s", hipGetErrorString(e));
+    return XSD_OK;
+}
+
 } // namespace
 
 #endif /* XSD_SW_GEMM_S3X_H */

@@ -1,7 +1,7 @@
 // sw_kernels.h -- the exact-fp32 kernels that the Swin-family networks (swinfir.hip, hat.hip, swinir.hip) share, with their launch helpers.
 //
 // Every product is an fp32 FMA on the fp32 matrix instruction v_mfma_f32_32x32x2_f32 (bitwise a k-ordered fmaf chain).  The GEMM's
-// fmaf chains are 16 long, their sums over K are carried in double, as are the LayerNorm statistics.  No float atomics anywhere and
+// fmaf chains are 16 long (4 where K <= 48), their sums over K are carried in double, as are the LayerNorm statistics.  No float atomics anywhere and
 // every reduction has a fixed order: an image's output is bitwise independent of the batch it shares and of the run.
 //
 // Feature maps are TOKEN-MAJOR ([B][H*W][C], C contiguous): the Swin blocks' (B, L, C) layout, and at the same time the NHWC view
@@ -59,6 +59,7 @@ constexpr int GM = 128;      // rows (tokens / pixels) per workgroup: wave w own
 constexpr int GN = 64;       // output columns per workgroup: two 32 x 32 accumulators per wave
 constexpr int GK = 16;       // K per LDS round
 constexpr int GAP = GM + 4;  // LDS row pitch of the A tile
+constexpr int GK_SHORT = 3 * GK;   // a sum of at most this many terms runs in fmaf chains of 4 instead of 16 (sw_gemm_kernel)
 
 enum { A_TOK = 0, A_CONV3 = 1 };
 enum { ACT_NONE = 0, ACT_GELU = 1, ACT_LRELU = 2 };
@@ -124,6 +125,7 @@ __device__ __forceinline__ void gemm_store_ext(const GemmP& P, float x, long lon
 #define SW_GEMM_EXT_SRC(yy, xx) ((long long)yy * P.W + xx)
 #endif
 
+template <bool SHORTK>      // SHORTK: K <= GK_SHORT (gemm() picks the instance)
 __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
 {
     __shared__ __attribute__((aligned(16))) float As[GK][GAP];
@@ -178,11 +180,28 @@ __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
         }
     };
 
-    // each K round is a 16-term fmaf chain on the MFMA from zero; the rounds are summed in double (a fixed order)
+    // each K round is a 16-term fmaf chain on the MFMA from zero; the rounds are summed in double (a fixed order).  A sum of at most
+    // GK_SHORT terms (conv_first from 1 to 5 channels, layers narrower than any published embed_dim) is cut into chains of 4 instead:
+    // there a correctly rounded sum is what the chain's roundings are measured against (at K = 36 chains of 16 left 2.5 x its
+    // max-relative error), and the four flushes per round are paid for three rounds at most.  Longer sums keep their bits and speed.
     double d0[16], d1[16];
 #pragma unroll
     for (int v = 0; v < 16; ++v) { d0[v] = 0.0; d1[v] = 0.0; }
     const int i32 = lane & 31, h2 = lane >> 5;
+    f32x16 acc0, acc1;
+    // steps [s0, s1) of a round as one chain from zero, added to the double sums
+    auto chain = [&](const int s0, const int s1) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; }
+#pragma unroll
+        for (int s = s0; s < s1; ++s) {
+            const float a = As[2 * s + h2][32 * wave + i32];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[2 * s + h2][i32], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[2 * s + h2][32 + i32], acc1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int v = 0; v < 16; ++v) { d0[v] += (double)acc0[v]; d1[v] += (double)acc1[v]; }
+    };
     load(0);
     for (int k0 = 0; k0 < P.K; k0 += GK) {
         __syncthreads();
@@ -192,17 +211,12 @@ __global__ __launch_bounds__(256) void sw_gemm_kernel(const GemmP P)
         for (int i = 0; i < 4; ++i) Bs[(tid >> 6) + 4 * i][tid & 63] = bv[i];
         __syncthreads();
         if (k0 + GK < P.K) load(k0 + GK);
-        f32x16 acc0, acc1;
+        if (SHORTK) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; }
-#pragma unroll
-        for (int s = 0; s < GK / 2; ++s) {
-            const float a = As[2 * s + h2][32 * wave + i32];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[2 * s + h2][i32], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Bs[2 * s + h2][32 + i32], acc1, 0, 0, 0);
+            for (int s = 0; s < GK / 2; s += 2) chain(s, s + 2);
+        } else {
+            chain(0, GK / 2);
         }
-#pragma unroll
-        for (int v = 0; v < 16; ++v) { d0[v] += (double)acc0[v]; d1[v] += (double)acc1[v]; }
     }
     // accumulator register v of lane l: row 32 wave + 8 (v / 4) + 4 (l / 32) + v % 4, column 32 c + l % 32
 #pragma unroll
@@ -437,7 +451,9 @@ hipError_t gemm(hipStream_t s, const GemmP& p)
 {
     const long long M = (long long)p.B * p.HW;
     dim3 grid((unsigned)((M + GM - 1) / GM), (unsigned)((p.N + GN - 1) / GN));
-    hipLaunchKernelGGL(sw_gemm_kernel, grid, dim3(256), 0, s, p);
+    // two instances, so that the long sums run the instruction stream they always ran
+    if (p.K <= GK_SHORT) hipLaunchKernelGGL(sw_gemm_kernel<true>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(sw_gemm_kernel<false>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

@@ -481,6 +481,9 @@ int xsd_sw_test_gemm(const float* dev_a, const float* dev_w, const float* dev_bi
     return test_gemm(dev_a, dev_w, dev_bias, dev_y, conv3, B, H, W, cin, N, ldy, act, slope, math, (hipStream_t)stream);
 }
 
+// One launch of this file's GEMM instances as the forwards describe theirs (tests): see include/xsd.h, xsd_sw_gemm_view.
+int xsd_sw_test_gemm_view(const xsd_sw_gemm_view* view, void* stream) { return test_gemm_view(view, (hipStream_t)stream); }
+
 // The shifted-window attention of both networks on its own (tests): see include/xsd.h, xsd_sw_test_attention.
 int xsd_sw_test_attention(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int shift,
                           float scale, void* stream)

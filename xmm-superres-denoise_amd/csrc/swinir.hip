@@ -414,4 +414,7 @@ int xsd_swinir_test_nearest_conv(const float* dev_a, const float* dev_w, const f
     return test_gemm(dev_a, dev_w, dev_bias, dev_y, 1, B, H, W, cin, N, N, ACT_LRELU, slope, math, (hipStream_t)stream, true);
 }
 
+// One launch of the SW_GEMM_EXT instances as the forward describes its own (tests): see include/xsd.h, xsd_swinir_test_gemm_view.
+int xsd_swinir_test_gemm_view(const xsd_sw_gemm_view* view, void* stream) { return test_gemm_view(view, (hipStream_t)stream); }
+
 } // extern "C"

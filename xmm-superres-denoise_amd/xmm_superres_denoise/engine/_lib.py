@@ -38,6 +38,16 @@ class XsdTestGconvArgs(ctypes.Structure):      # xsd_test_gconv_args (include/xs
                 ("pre", ctypes.c_void_p), ("clamp01", ctypes.c_int32)]
 
 
+class XsdSwGemmView(ctypes.Structure):      # xsd_sw_gemm_view (include/xsd.h): one launch of the Swin GEMM as the forwards describe theirs
+    _fields_ = [("conv3", ctypes.c_int32), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("cin", ctypes.c_int32),
+                ("N", ctypes.c_int32), ("a", ctypes.c_void_p), ("a_nchw", ctypes.c_int32), ("lda", ctypes.c_int64),
+                ("imean", ctypes.c_void_p), ("irange", ctypes.c_float), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("act", ctypes.c_int32), ("slope", ctypes.c_float), ("res", ctypes.c_void_p), ("rbs", ctypes.c_int64), ("rps", ctypes.c_int64),
+                ("omode", ctypes.c_int32), ("y", ctypes.c_void_p), ("ldy", ctypes.c_int64), ("r", ctypes.c_int32), ("omean", ctypes.c_void_p),
+                ("orange", ctypes.c_float), ("math", ctypes.c_int32), ("rnchw", ctypes.c_int32), ("cH", ctypes.c_int32), ("cW", ctypes.c_int32),
+                ("up2", ctypes.c_int32)]
+
+
 class XsdRestormerConfig(ctypes.Structure):
     _fields_ = [("inp_channels", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("dim", ctypes.c_int32),
                 ("num_blocks", ctypes.c_int32 * 4), ("num_refinement_blocks", ctypes.c_int32), ("heads", ctypes.c_int32 * 4),
@@ -185,6 +195,8 @@ def load():
     L.xsd_swinir_test_pad.argtypes = [fp, fp, i32, i32, i32, i32, i32, ctypes.POINTER(f32), f32, vp]
     L.xsd_swinir_test_nearest_conv.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, f32, i32, vp]
     L.xsd_sw_test_gemm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i64, i32, f32, i32, vp]
+    L.xsd_sw_test_gemm_view.argtypes = [ctypes.POINTER(XsdSwGemmView), vp]
+    L.xsd_swinir_test_gemm_view.argtypes = [ctypes.POINTER(XsdSwGemmView), vp]
     L.xsd_hat_test_ocab.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
     L.xsd_hat_test_channel_mean.argtypes = [fp, fp, i32, i64, i32, vp]
     L.xsd_sw_test_attention.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, f32, vp]
@@ -224,6 +236,7 @@ ABI_SYMBOLS = [
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
+    "xsd_sw_test_gemm_view", "xsd_swinir_test_gemm_view",
     "xsd_hat_create", "xsd_hat_destroy", "xsd_hat_param_count", "xsd_hat_pack_weights", "xsd_hat_forward", "xsd_hat_test_ocab",
     "xsd_hat_test_channel_mean", "xsd_hat_set_math", "xsd_hat_get_math",
     "xsd_sw_test_attention", "xsd_sw_test_layernorm", "xsd_hat_test_ca_combine",

@@ -509,6 +509,51 @@ def sw_conv3x3(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = Non
     return y if out is not None else y.view(B, H, W, -1)
 
 
+SW_OMODE = {"tok": 0, "shuffle": 1, "nchw": 2, "shuffle_nchw": 3}
+
+
+@_on_tensor_device
+def sw_gemm_view(a: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, conv3: bool, B: int, H: int, W: int, cin: int, N: int,
+                 ext: bool = False, a_nchw: bool = False, lda: int = 0, imean: torch.Tensor | None = None, irange: float = 1.0,
+                 bias: torch.Tensor | None = None, act: str | None = None, slope: float = 0.0, res: torch.Tensor | None = None,
+                 rbs: int = 0, rps: int = 0, omode: str = "tok", ldy: int = 0, r: int = 1, omean: torch.Tensor | None = None,
+                 orange: float = 1.0, math: str = "fp32", rnchw: bool = False, cH: int = 0, cW: int = 0, up2: bool = False) -> torch.Tensor:
+    """One launch of the Swin GEMM described as the forwards describe theirs (include/xsd.h: xsd_sw_gemm_view), on the instance SwinFIR
+    runs or, with `ext`, on SwinIR's.  Tensors stand for device addresses only: the kernel reads and writes from each tensor's first
+    element with the strides given here, so a view that starts inside a larger buffer (a column slice, a shifted base) is passed as
+    that view.  The caller sizes the buffers.  Returns y."""
+    for name, t in (("a", a), ("w", w), ("y", y), ("bias", bias), ("res", res), ("imean", imean), ("omean", omean)):
+        if t is None:
+            if name in ("a", "w", "y"):
+                raise XsdError(f"{name} is missing")
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise XsdError(f"{name} must be a float32 CUDA(HIP) tensor")
+    if act not in SW_ACT:
+        raise XsdError(f"unknown activation {act!r}: {list(SW_ACT)}")
+    if math not in SW_MATH:
+        raise XsdError(f"unknown math mode {math!r}: the modes are {sorted(SW_MATH)}")
+    if omode not in SW_OMODE:
+        raise XsdError(f"unknown omode {omode!r}: {list(SW_OMODE)}")
+    if w.numel() != N * cin * (9 if conv3 else 1) or not w.is_contiguous():
+        raise XsdError(f"w {tuple(w.shape)} is not the contiguous [N = {N}, cin = {cin}{', 3, 3' if conv3 else ''}] weight")
+    if bias is not None and bias.numel() != N:
+        raise XsdError(f"bias has {bias.numel()} elements for {N} outputs")
+    if imean is not None and imean.numel() != cin:
+        raise XsdError(f"imean has {imean.numel()} elements for {cin} input channels")
+    nmean = N if omode == "nchw" else N // max(1, r * r)
+    if omean is not None and omean.numel() != nmean:
+        raise XsdError(f"omean has {omean.numel()} elements for {nmean} output channels")
+    v = _lib.XsdSwGemmView(conv3=int(bool(conv3)), B=int(B), H=int(H), W=int(W), cin=int(cin), N=int(N), a=a.data_ptr(),
+                           a_nchw=int(bool(a_nchw)), lda=int(lda), imean=_ptr(imean), irange=float(irange), w=w.data_ptr(),
+                           bias=_ptr(bias), act=SW_ACT[act], slope=float(slope), res=_ptr(res), rbs=int(rbs), rps=int(rps),
+                           omode=SW_OMODE[omode], y=y.data_ptr(), ldy=int(ldy), r=int(r), omean=_ptr(omean), orange=float(orange),
+                           math=SW_MATH[math], rnchw=int(bool(rnchw)), cH=int(cH), cW=int(cW), up2=int(bool(up2)))
+    L = _lib.load()
+    check((L.xsd_swinir_test_gemm_view if ext else L.xsd_sw_test_gemm_view)(ctypes.byref(v), _stream_ptr(a.device)))
+    return y
+
+
 @_on_tensor_device
 def hat_channel_mean(x: torch.Tensor) -> torch.Tensor:
     """The channel attention's global average pool on its own (include/xsd.h: xsd_hat_test_channel_mean): x [B, HW, C] token-major ->
