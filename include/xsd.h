@@ -786,6 +786,32 @@ int xsd_loss_test_pool2(const float* dev_p, const float* dev_t, float* dev_po, f
 /* launch_clamp_bwd alone (csrc/aux_kernels.hip): dpre = (0 <= pre <= 1) ? dy : 0 over n elements. */
 int xsd_test_clamp_bwd(const float* dev_pre, const float* dev_dy, float* dev_dpre, int64_t n, void* stream);
 
+/* Test entry, in the product library like xsd_ext_metrics_test_stage (host code only, on no product path; synchronous): copy ONE region
+ * of what the last xsd_pack_weights of a plane-path engine produced into dev_dst (device memory, dst_bytes long).  info[0] (host)
+ * receives the region's size in bytes; with dev_dst NULL the call reports the size only.  A region may be empty (0 bytes: PK_SBIAS
+ * of a DN engine, PARAMS_PAD of a width that is a multiple of 32).
+ *   PK_FWD, PK_BWD, PK_FWD_S, PK_BWD_S   pk_floats x 4 B each (what they hold depends on the math mode: xsd_set_math)
+ *   AMAX         2 floats: max |x| of the forward and of the input-gradient panels (math mode f16x3)
+ *   PK_EDGE      [first_fwd | first_bwd][in channel][plane][tap][c], [last_fwd | last_bwd][out channel][plane][tap][c]
+ *   PK_SBIAS     the pixel-shuffle convs' biases in chunk order, 128 planes floats per conv
+ *   PARAMS_PAD   the zero-padded flat parameter vector of a width that is no multiple of 32
+ *   TABLE        HOST data, copied to a HOST buffer dev_dst, int64 words: ndesc, nup, first_w, last_w, planes, nf_pad (0: not padded),
+ *                pk_floats, floats of the flat vector the offsets refer to (the padded one if there is one); then per pack descriptor
+ *                (read back from the device table the pack kernels use) src_w, dst_fwd, dst_bwd, cout, cin, shuffle, the bits of
+ *                bwd_scale; then per pixel-shuffle conv b_off, sbias_off.
+ * Refused, copying nothing: XSD_ERR_ARG for null e / info, a generic-width engine, an unknown region, a buffer too small;
+ * XSD_ERR_STATE before the first xsd_pack_weights. */
+enum {
+    XSD_PACKED_PK_FWD = 0, XSD_PACKED_PK_BWD, XSD_PACKED_PK_FWD_S, XSD_PACKED_PK_BWD_S, XSD_PACKED_AMAX, XSD_PACKED_PK_EDGE,
+    XSD_PACKED_PK_SBIAS, XSD_PACKED_PARAMS_PAD, XSD_PACKED_TABLE, XSD_PACKED_REGIONS
+};
+int xsd_test_packed_region(xsd_engine* e, int region, void* dev_dst, int64_t dst_bytes, int64_t* info, void* stream);
+/* The gather direction of the zero-padded widths alone: exactly the launch xsd_backward_stage makes, over all descriptors at once, from
+ * the caller's padded gradient vector (TABLE word 7 floats) into the caller's real-width one.  XSD_ERR_ARG when the width is not padded. */
+int xsd_test_pad_gather(xsd_engine* e, float* dev_grads_real, const float* dev_grads_padded, void* stream);
+/* launch_add_channels alone (csrc/aux_kernels.hip): dst[B][HW] += sum over the C channels of src[B][C][HW]. */
+int xsd_test_add_channels(float* dev_dst, const float* dev_src, int C, int64_t HW, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,8 +25,10 @@ __device__ __forceinline__ void publish_block_max(float m, float* slot)
 }
 
 // torch.clamp propagates NaN (clamp(nan, 0, 1) = nan; +-inf go to the bounds); fminf / fmaxf alone return the non-NaN operand and
-// would turn a NaN pixel into 0.  Identical to fminf(fmaxf(v, lo), hi) for every non-NaN v (round 6: tests/test_hip_abi_errors.py).
-__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+// would turn a NaN pixel into 0 (round 6: tests/test_hip_abi_errors.py).  Written as torch's two selects: both comparisons are false
+// for a NaN, and for a -0.0 at a lower bound of 0, which clamp_ keeps and fmaxf(-0.0, 0.f) turned into +0.0
+// (tests/test_hip_transform_kernels.py); every other value gets what fminf(fmaxf(v, lo), hi) gave it.
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -483,7 +485,9 @@ __device__ __forceinline__ float stretch_fwd(float v, int mode)
     switch (mode) {
     case 1: return sqrtf(v);                                        // torch.sqrt     (normalize.py:56-57)
     case 2: return asinhf(v / 0.02f) / asinhf(1.0f / 0.02f);        // _asinh         (normalize.py:4-11)
-    case 3: return logf(1000.f * v + 1.f) / logf(1000.f);           // _log           (normalize.py:23-26)
+    // _log (normalize.py:23-26), in double: the device's logf rests on the hardware's log2 approximation (0.86 ulp rms, 2.4 ulp at worst
+    // over [1, 1001]: 2.4 x the error of torch's fp32 CPU evaluation of the whole stretch, which is all but correctly rounded)
+    case 3: return (float)(log(1000.0 * (double)v + 1.0) / log(1000.0));
     default: return v;
     }
 }

@@ -1878,4 +1878,68 @@ int xsd_test_clamp_bwd(const float* dev_pre, const float* dev_dy, float* dev_dpr
     return XSD_OK;
 }
 
+int xsd_test_packed_region(xsd_engine* e, int region, void* dev_dst, int64_t dst_bytes, int64_t* info, void* stream)
+{
+    if (!e || !info) return fail(XSD_ERR_ARG, "null argument");
+    if (e->generic) return fail(XSD_ERR_ARG, "xsd_test_packed_region: a generic-width engine has no plane panels");
+    if (region < 0 || region >= XSD_PACKED_REGIONS) return fail(XSD_ERR_ARG, "xsd_test_packed_region: unknown region %d", region);
+    if (!e->packed) return fail(XSD_ERR_STATE, "xsd_test_packed_region needs a preceding xsd_pack_weights");
+    const int ci = e->cfg.in_channels, co = e->cfg.out_channels, nup = (int)e->up.size();
+    const void* src = nullptr;
+    int64_t bytes = 0;
+    std::vector<int64_t> table;
+    switch (region) {
+    case XSD_PACKED_PK_FWD: src = e->pk_fwd; bytes = 4 * e->pk_floats; break;
+    case XSD_PACKED_PK_BWD: src = e->pk_bwd; bytes = 4 * e->pk_floats; break;
+    case XSD_PACKED_PK_FWD_S: src = e->pk_fwd_s; bytes = 4 * e->pk_floats; break;
+    case XSD_PACKED_PK_BWD_S: src = e->pk_bwd_s; bytes = 4 * e->pk_floats; break;
+    case XSD_PACKED_AMAX: src = e->amax; bytes = 2 * 4; break;
+    case XSD_PACKED_PK_EDGE: src = e->pk_edge; bytes = 4ll * 2 * 288 * e->planes * (ci + co); break;
+    case XSD_PACKED_PK_SBIAS: src = e->pk_sbias; for (auto& c : e->up) bytes += 4ll * c.cout; break;
+    case XSD_PACKED_PARAMS_PAD: src = e->params_pad; bytes = e->nf_pad ? 4 * e->nparams_pad : 0; break;
+    default: {  // XSD_PACKED_TABLE: the descriptors the pack kernels read, copied back from the device
+        std::vector<PackDesc> descs(e->ndesc);
+        HIPCHK(hipMemcpy(descs.data(), e->descs_dev, sizeof(PackDesc) * descs.size(), hipMemcpyDeviceToHost));
+        table = {e->ndesc, nup, e->first_w, e->last_w, e->planes, e->nf_pad, e->pk_floats, e->nf_pad ? e->nparams_pad : e->nparams};
+        for (auto& d : descs) {
+            unsigned int bits; memcpy(&bits, &d.bwd_scale, 4);
+            table.insert(table.end(), {d.src_w, d.dst_fwd, d.dst_bwd, d.cout, d.cin, d.shuffle, (int64_t)bits});
+        }
+        for (auto& c : e->up) table.insert(table.end(), {c.b_off, c.sbias_off});
+        bytes = 8 * (int64_t)table.size();
+    } }
+    info[0] = bytes;
+    if (!dev_dst) return XSD_OK;
+    if (dst_bytes < bytes) return fail(XSD_ERR_ARG, "xsd_test_packed_region: region %d holds %lld bytes, the buffer %lld", region, (long long)bytes, (long long)dst_bytes);
+    if (bytes == 0) return XSD_OK;
+    if (region == XSD_PACKED_TABLE) { memcpy(dev_dst, table.data(), (size_t)bytes); return XSD_OK; }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t err = hipMemcpyAsync(dev_dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "packed region %d: %s", region, hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_pad_gather(xsd_engine* e, float* dev_grads_real, const float* dev_grads_padded, void* stream)
+{
+    if (!e || !dev_grads_real || !dev_grads_padded) return fail(XSD_ERR_ARG, "null argument");
+    if (e->generic || !e->nf_pad) return fail(XSD_ERR_ARG, "xsd_test_pad_gather: the engine's width is not zero-padded");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(pad_params_kernel, dim3(64, e->npad), dim3(256), 0, s, dev_grads_real, const_cast<float*>(dev_grads_padded), static_cast<const PadDesc*>(e->pad_descs), 1);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "pad gather: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+int xsd_test_add_channels(float* dev_dst, const float* dev_src, int C, int64_t HW, int B, void* stream)
+{
+    if (!dev_dst || !dev_src || C < 1 || HW < 1 || B < 1) return fail(XSD_ERR_ARG, "null argument or an extent < 1");
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t err = launch_add_channels(dev_dst, dev_src, C, HW, B, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "add channels: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
 } // extern "C"

@@ -155,6 +155,9 @@ def load():
     L.xsd_loss_test_scale.argtypes = [vp, fp, fp, fp, fp, fp, i32, vp, ctypes.POINTER(f32), i32, i32, i32, vp]
     L.xsd_loss_test_pool2.argtypes = [fp, fp, fp, fp, i32, i32, i32, vp]
     L.xsd_test_clamp_bwd.argtypes = [fp, fp, fp, i64, vp]
+    L.xsd_test_packed_region.argtypes = [vp, i32, vp, i64, ctypes.POINTER(i64), vp]
+    L.xsd_test_pad_gather.argtypes = [vp, fp, fp, vp]
+    L.xsd_test_add_channels.argtypes = [fp, fp, i32, i64, i32, vp]
     L.xsd_restormer_create.argtypes = [ctypes.POINTER(XsdRestormerConfig), ctypes.POINTER(vp)]
     L.xsd_restormer_destroy.argtypes = [vp]
     L.xsd_restormer_destroy.restype = None
@@ -232,7 +235,7 @@ ABI_SYMBOLS = [
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_ext_metrics_create", "xsd_ext_metrics_destroy", "xsd_ext_metrics_eval", "xsd_ext_metrics_test_stage", "xsd_fsim_create", "xsd_fsim_destroy", "xsd_fsim_eval", "xsd_fsim_test_dft2", "xsd_fsim_test_median", "xsd_fsim_test_stage", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_compose_batch", "xsd_normalize", "xsd_image_upsample",
     "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd", "xsd_test_conv3x3_ex", "xsd_test_wgrad_ex",
     "xsd_test_edge_expand", "xsd_test_edge_reduce", "xsd_test_edge_wgrad", "xsd_test_gconv", "xsd_test_gwgrad", "xsd_test_gop", "xsd_test_gpack",
-    "xsd_loss_test_scale", "xsd_loss_test_pool2", "xsd_test_clamp_bwd",
+    "xsd_loss_test_scale", "xsd_loss_test_pool2", "xsd_test_clamp_bwd", "xsd_test_packed_region", "xsd_test_pad_gather", "xsd_test_add_channels",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
     "xsd_swinfir_create", "xsd_swinfir_destroy", "xsd_swinfir_param_count", "xsd_swinfir_pack_weights", "xsd_swinfir_forward",
     "xsd_swinfir_fft_supported", "xsd_swinfir_test_fft", "xsd_swinfir_set_math", "xsd_swinfir_get_math", "xsd_sw_test_gemm",
