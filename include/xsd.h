@@ -713,6 +713,19 @@ int xsd_test_conv3x3_ex(xsd_engine* e, const float* const* host_in_planes, int n
 int xsd_test_wgrad_ex(xsd_engine* e, const float* const* host_x_planes, int n_in, const float* const* host_g_planes, int n_g, int shuffle_g,
                       float scale, int shuffle, int plane, int j0, int n0, int cin_total, int cout_total,
                       float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream);
+/* A dense block's weight gradients as the plan of the shipped configuration launches them (kernel-level tests; synchronous; split math
+ * modes only): ONE pair-list launch over the fifteen (x_j, G_n) pairs, j <= n, then the five convs' fixed-order reductions as one launch
+ * (separate_reduces != 0: as five).  host_x_planes: x_0 .. x_4, host_g_planes: G_1 .. G_5 (host arrays of five device planes
+ * [B][H][W][32]).  Conv n + 1 (n = 0 .. 4) owns dw [32][32 (n + 1)][3][3] (OIHW) at dev_grads + host_w_off[n] and db [32] at
+ * dev_grads + host_b_off[n]; conv 5's are multiplied by gscale.  nparts 0: the plan's own count for this device (the function the plan
+ * asks), else 8 m or 8 m + 1 with 1 <= m <= 10; *host_nparts (or NULL) = what ran.  The launch and the reductions are filled by the
+ * function the plan calls.  Both partial-sum buffers of the engine are filled with 0xFF bytes before the launch: a panel or bias row
+ * that no workgroup writes arrives as NaN.  In f16x3 the ten planes' max |x| are reduced here.  Refused with XSD_ERR_ARG, nothing
+ * launched: an engine in fp32 mode or of the generic-width path, a null plane, an nparts of another form or one whose 15 panels or
+ * 5 x 32 bias sums per part the partial-sum buffers do not hold. */
+int xsd_test_wgrad_block(xsd_engine* e, const float* const* host_x_planes, const float* const* host_g_planes, float gscale, float* dev_grads,
+                         const long long* host_w_off, const long long* host_b_off, int nparts, int separate_reduces, int* host_nparts,
+                         int B, int H, int W, void* stream);
 
 /* The edge layers one by one (csrc/aux_kernels.hip; kernel-level tests; synchronous; an engine of the plane path).  Every hook packs
  * ONE (32, 9) weight block with the engine's own packer (pack_edge_kernel) and launches through the engine's own launcher.

@@ -178,6 +178,66 @@ static int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
     return e->nparts;
 }
 
+// A dense block's FIFTEEN (X_j, G_n) pairs (conv n + 1 reads x_0 .. x_n: j <= n) as ONE pair-list launch (Builder::wgrad_block_launch)
+// plus the five convs' reductions.  The plan and the block test hook (xsd_test_wgrad_block) both fill their launch here, so the hook
+// cannot drift from the plan: the part count, the pair list, where each conv's panels and bias sums start, the strides, the scales.
+// m parts per XCD, each 15 workgroups side by side: m = CUs / (8 x 15), at most 10 ((8 m + 1) x 15 partial panels must fit
+// wg_partial's 256 x 5); m = 0 (fewer than 120 CUs): the plan runs one launch per G instead
+static int block_parts_per_xcd(int ncu) { const int m = ncu / 120; return m > 10 ? 10 : m; }
+static int wgrad_block_nparts(const xsd_engine* e)
+{
+    // (MI355X: 256 CUs -> 16 parts = 240 workgroups; the kernel's decode takes any nparts = 8 m or 8 m + 1)
+    const int m = block_parts_per_xcd(e->ncu);
+    // one more part on the CUs the 8 m x 15 workgroups leave, when those can hold its 15 slots two per XCD (>= 16 spare CUs;
+    // MI355X: exactly 16): no L2 sharing for it, no idle CU
+    // (XSD_WGRAD_TAIL=0 (include/xsd.h): 8 m parts; same device 124.7 -> 125.2 tiles/s, the kernel -1.9 %)
+#ifdef XSD_TEST_HOOKS      // only the hooks variant of the library (make hooks; include/xsd.h) reads the environment here
+    static const int tail = getenv("XSD_WGRAD_TAIL") ? atoi(getenv("XSD_WGRAD_TAIL")) : 1;
+#else
+    constexpr int tail = 1;
+#endif
+    return (tail && e->ncu - 120 * m >= 16) ? 8 * m + 1 : 8 * m;
+}
+struct WgradBlock {
+    WgradParams wp;               // the pair-list launch; the caller sets the planes, their max-|x| slots and the late-bound pointers
+    WgradReduceParams rp[5];      // conv n + 1's reduction; the caller sets dw and db
+};
+// `k.wp` comes from Builder::wgrad_base; cin[n], cout[n]: the OIHW extent of conv n + 1's gradient; gscale: conv 5's factor
+static void wgrad_block_fill(WgradBlock& k, int nparts, const int cin[5], const int cout[5], float gscale, float* partial, float* bias_partial)
+{
+    WgradParams& wp = k.wp;
+    wp.n_in = 5; wp.n_g = 5; wp.nparts = nparts; wp.npairs = 15;
+    wp.partial = partial; wp.bias_partial = bias_partial;
+    // slots are conv-major (conv 5 first), so conv n's blocks are contiguous and each conv gets its own fixed-order reduce
+    int first[5], slot = 0;
+    wp.pair_j = 0; wp.pair_n = 0;
+    for (int n = 4; n >= 0; --n) {
+        first[n] = slot;
+        for (int j = 0; j <= n; ++j, ++slot) { wp.pair_j |= (unsigned long long)j << (4 * slot); wp.pair_n |= (unsigned long long)n << (4 * slot); }
+    }
+    for (int n = 0; n < 5; ++n) {
+        WgradReduceParams& r = k.rp[n];
+        memset(&r, 0, sizeof(r));
+        r.nparts = nparts; r.n_in = n + 1; r.n_g = 1; r.cin_total = cin[n]; r.cout_total = cout[n];
+        r.shuffle = 0; r.scale = n == 4 ? gscale : 1.f;
+        r.part_stride = (long long)wp.npairs * PANEL_FLOATS; r.bias_stride = wp.n_g * 32;
+        r.partial = partial + (long long)first[n] * PANEL_FLOATS; r.bias_partial = bias_partial + n * 32;
+    }
+}
+// the five convs' fixed-order reductions as one launch (bitwise what five launches give: `separate`, the test hook's other form)
+static hipError_t wgrad_block_reduce(const WgradBlock& k, bool separate, hipStream_t s)
+{
+    if (separate) {
+        for (int n = 0; n < 5; ++n) { hipError_t err = launch_wgrad_reduce(k.rp[n], s); if (err != hipSuccess) return err; }
+        return hipSuccess;
+    }
+    WgradReduceBatch rb;
+    memset(&rb, 0, sizeof(rb));
+    rb.n = 5;
+    for (int n = 0; n < 5; ++n) rb.r[n] = k.rp[n];
+    return launch_wgrad_reduce_multi(rb, s);
+}
+
 // Workgroups (partial sums) of one edge weight-gradient launch: the plan and the single-launch test hook (xsd_test_edge_wgrad) both ask
 // here.  A constant: the kernel strides over the image rows, idle workgroups store zeros, edge_partial holds this many records.
 static int edge_wgrad_nblocks() { return EDGE_WGRAD_BLOCKS; }
@@ -472,69 +532,35 @@ struct Builder {
     // every G tile comes from HBM once and from that XCD's L2 for the other pairs (10 planes read instead of the 20 of five
     // launches per G).  The step runs at the package power cap and HBM traffic is a third of a launch's dynamic energy
     // (DESIGN.md 6.5): bytes are what there is to save; the 16 CUs the launch leaves idle draw next to nothing.
-    // Slots are conv-major (conv 5 first), so conv n's blocks are contiguous and each conv gets its own fixed-order reduce.
-    static int block_parts_per_xcd(int ncu) { const int m = ncu / 120; return m > 10 ? 10 : m; }     // ((8 m + 1) x 15 partial panels must fit wg_partial's 256 x 5)
+    // The part count, the pair list (conv-major) and the five reductions' fields: wgrad_block_fill above, shared with xsd_test_wgrad_block;
+    // the caller falls back to one launch per G when block_parts_per_xcd is 0.
     void wgrad_block_launch(std::vector<Launch>& ops, const Tensor* const xpl[5], const Tensor* const Gp[6], const ConvW* cw, float gscale)
     {
         xsd_engine* eng = e;
-        WgradParams wp = wgrad_base(0);
-        // m parts per XCD, each 15 workgroups side by side: m = CUs / (8 x 15) (MI355X: 256 CUs -> 16 parts = 240 workgroups; the
-        // kernel's decode takes any nparts = 8 m or 8 m + 1; the caller falls back to one launch per G when m = 0)
-        const int m = block_parts_per_xcd(e->ncu);
-        wp.n_in = 5; wp.n_g = 5; wp.nparts = 8 * m; wp.npairs = 15;
-        // one more part on the CUs the 8 m x 15 workgroups leave, when those can hold its 15 slots two per XCD (>= 16 spare CUs;
-        // MI355X: exactly 16): no L2 sharing for it, no idle CU
-        // (XSD_WGRAD_TAIL=0 (include/xsd.h): 8 m parts; same device 124.7 -> 125.2 tiles/s, the kernel -1.9 %)
-#ifdef XSD_TEST_HOOKS      // only the hooks variant of the library (make hooks; include/xsd.h) reads the environment here
-        static const int tail = getenv("XSD_WGRAD_TAIL") ? atoi(getenv("XSD_WGRAD_TAIL")) : 1;
-#else
-        constexpr int tail = 1;
-#endif
-        if (tail && e->ncu - 120 * m >= 16) wp.nparts = 8 * m + 1;
+        WgradBlock k;
+        k.wp = wgrad_base(0);
         std::vector<Launch> pre;
         for (int i = 0; i < 5; ++i) {
-            wp.x[i] = std_in((*xpl[i])[0], 0); wp.g[i] = std_in((*Gp[i + 1])[0], 0);      // g[n] = G_{n+1}, the gradient at conv n+1's output
+            k.wp.x[i] = std_in((*xpl[i])[0], 0); k.wp.g[i] = std_in((*Gp[i + 1])[0], 0);      // g[n] = G_{n+1}, the gradient at conv n+1's output
             if (e->math == 4) {
-                wp.amax_x[i] = slot_of(wp.x[i], wp.H, wp.W, pre);
-                wp.amax_g[i] = slot_of(wp.g[i], wp.H, wp.W, pre);
+                k.wp.amax_x[i] = slot_of(k.wp.x[i], k.wp.H, k.wp.W, pre);
+                k.wp.amax_g[i] = slot_of(k.wp.g[i], k.wp.H, k.wp.W, pre);
             }
         }
-        int first[5], slot = 0;
-        for (int n = 4; n >= 0; --n) {
-            first[n] = slot;
-            for (int j = 0; j <= n; ++j, ++slot) { wp.pair_j |= (unsigned long long)j << (4 * slot); wp.pair_n |= (unsigned long long)n << (4 * slot); }
-        }
-        WgradReduceParams rp[5];
-        long long w_off[5], b_off[5];
-        for (int n = 0; n < 5; ++n) {
-            memset(&rp[n], 0, sizeof(rp[n]));
-            rp[n].nparts = wp.nparts; rp[n].n_in = n + 1; rp[n].n_g = 1; rp[n].cin_total = cw[n].cin; rp[n].cout_total = cw[n].cout;
-            rp[n].shuffle = 0; rp[n].scale = n == 4 ? gscale : 1.f;
-            rp[n].part_stride = (long long)wp.npairs * PANEL_FLOATS; rp[n].bias_stride = wp.n_g * 32;
-            w_off[n] = cw[n].w_off; b_off[n] = cw[n].b_off;
-        }
-        const double px = (double)wp.B * wp.H * wp.W;
+        int cin[5], cout[5];
+        std::vector<long long> wo(5), bo(5);
+        for (int n = 0; n < 5; ++n) { cin[n] = cw[n].cin; cout[n] = cw[n].cout; wo[n] = cw[n].w_off; bo[n] = cw[n].b_off; }
+        wgrad_block_fill(k, wgrad_block_nparts(e), cin, cout, gscale, e->wg_partial, e->wg_bias_partial);
+        const double px = (double)k.wp.B * k.wp.H * k.wp.W;
         const double flop = 2.0 * 9 * 32 * 32 * 15 * px;
         const double bytes = 128.0 * 10 * px;      // SURVEY 8(d) rule: every X plane and every G plane once
-        std::vector<long long> wo(w_off, w_off + 5), bo(b_off, b_off + 5);
-        std::vector<WgradReduceParams> rps(rp, rp + 5);
-        std::vector<int> fst(first, first + 5);
-        ops.push_back([eng, wp, rps, fst, pre, wo, bo, flop, bytes](hipStream_t s) mutable {
+        ops.push_back([eng, k, pre, wo, bo, flop, bytes](hipStream_t s) mutable {
             for (auto& f : pre) { hipError_t perr = f(s); if (perr != hipSuccess) return perr; }
-            wp.partial = eng->wg_partial; wp.bias_partial = eng->wg_bias_partial;
-            wp.zero = eng->zero_page; wp.ablate = eng->ablate; wp.dbg = eng->dbg;
-            hipError_t err = prof_launch(eng, PK_WGRAD, flop, bytes, s, [&]() { return launch_wgrad_split(eng->math, eng->ablate, wp, s); });
+            k.wp.zero = eng->zero_page; k.wp.ablate = eng->ablate; k.wp.dbg = eng->dbg;
+            hipError_t err = prof_launch(eng, PK_WGRAD, flop, bytes, s, [&]() { return launch_wgrad_split(eng->math, eng->ablate, k.wp, s); });
             if (err != hipSuccess) return err;
-            WgradReduceBatch rb;      // the five convs' fixed-order reductions as one launch (bitwise what five launches gave)
-            memset(&rb, 0, sizeof(rb));
-            rb.n = 5;
-            for (int n = 0; n < 5; ++n) {
-                WgradReduceParams r = rps[n];
-                r.partial = eng->wg_partial + (long long)fst[n] * PANEL_FLOATS; r.bias_partial = eng->wg_bias_partial + n * 32;
-                r.dw = eng->b_grads + wo[n]; r.db = eng->b_grads + bo[n];
-                rb.r[n] = r;
-            }
-            return launch_wgrad_reduce_multi(rb, s);
+            for (int n = 0; n < 5; ++n) { k.rp[n].dw = eng->b_grads + wo[n]; k.rp[n].db = eng->b_grads + bo[n]; }
+            return wgrad_block_reduce(k, false, s);
         });
     }
 
@@ -1665,6 +1691,51 @@ int xsd_test_wgrad_ex(xsd_engine* e, const float* const* x_planes, int n_in, con
     }
     if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
     if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient launch: %s", hipGetErrorString(err));
+    return XSD_OK;
+}
+
+// A dense block's pair-list weight-gradient launch plus the five convs' reductions (include/xsd.h): the launch and the reductions are
+// filled by wgrad_block_fill, the function the plan calls; both partial-sum buffers are all-ones bytes (NaN) when the launch starts.
+int xsd_test_wgrad_block(xsd_engine* e, const float* const* x_planes, const float* const* g_planes, float gscale, float* dev_grads,
+                         const long long* w_off, const long long* b_off, int nparts, int separate_reduces, int* host_nparts,
+                         int B, int H, int W, void* stream)
+{
+    if (!e || !x_planes || !g_planes || !dev_grads || !w_off || !b_off || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
+    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
+    if (e->math < 3) return fail(XSD_ERR_ARG, "the pair-list launch belongs to the split math modes (bf16x6, f16x3)");
+    for (int i = 0; i < 5; ++i) if (!x_planes[i] || !g_planes[i]) return fail(XSD_ERR_ARG, "null X or G plane");
+    for (int n = 0; n < 5; ++n) if (w_off[n] < 0 || b_off[n] < 0) return fail(XSD_ERR_ARG, "negative gradient offset");
+    if (nparts == 0) nparts = wgrad_block_nparts(e);
+    const int m = nparts >> 3;
+    if (nparts < 8 || (nparts & 7) > 1 || m > 10) return fail(XSD_ERR_ARG, "nparts = %d: a pair-list launch runs 8 m or 8 m + 1 parts, 1 <= m <= 10", nparts);
+    // wg_partial holds e->nparts x 5 panels, wg_bias_partial e->nparts x 4 x 32 sums (xsd_create)
+    if ((long long)nparts * 15 > (long long)e->nparts * 5 || (long long)nparts * 5 * 32 > (long long)e->nparts * 4 * 32)
+        return fail(XSD_ERR_ARG, "15 panels and 5 x 32 bias sums of %d parts do not fit the partial-sum buffers", nparts);
+    hipStream_t s = (hipStream_t)stream;
+    Builder b(e, B, H, W, false, 0);
+    WgradBlock k;
+    k.wp = b.wgrad_base(0);
+    for (int i = 0; i < 5; ++i) { k.wp.x[i] = b.std_in(x_planes[i], 0); k.wp.g[i] = b.std_in(g_planes[i], 0); }
+    int cin[5], cout[5];
+    for (int n = 0; n < 5; ++n) { cin[n] = 32 * (n + 1); cout[n] = 32; }
+    wgrad_block_fill(k, nparts, cin, cout, gscale, e->wg_partial, e->wg_bias_partial);
+    for (int n = 0; n < 5; ++n) { k.rp[n].dw = dev_grads + w_off[n]; k.rp[n].db = dev_grads + b_off[n]; }
+    k.wp.zero = e->zero_page; k.wp.ablate = e->ablate;
+    hipError_t err = hipSuccess;
+    if (e->math == 4) {   // nobody has reported the operands' max |x|: reduce them here (the weight-gradient hooks' slots, CAP-16 .. CAP-7)
+        float* t = e->amax + e->amax_cap - 16;
+        err = hipMemsetAsync(t, 0, 12 * sizeof(float), s);
+        for (int i = 0; i < 5 && err == hipSuccess; ++i) { err = launch_plane_amax(k.wp.x[i], B, H, W, t + i, s); k.wp.amax_x[i] = t + i; }
+        for (int i = 0; i < 5 && err == hipSuccess; ++i) { err = launch_plane_amax(k.wp.g[i], B, H, W, t + 5 + i, s); k.wp.amax_g[i] = t + 5 + i; }
+    }
+    // a panel or a bias row that no workgroup writes reaches dw / db as NaN, not as the previous launch's value
+    if (err == hipSuccess) err = hipMemsetAsync(e->wg_partial, 0xFF, sizeof(float) * (size_t)e->nparts * 5 * PANEL_FLOATS, s);
+    if (err == hipSuccess) err = hipMemsetAsync(e->wg_bias_partial, 0xFF, sizeof(float) * (size_t)e->nparts * 4 * 32, s);
+    if (err == hipSuccess) err = launch_wgrad_split(e->math, e->ablate, k.wp, s);
+    if (err == hipSuccess) err = wgrad_block_reduce(k, separate_reduces != 0, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
+    if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient block launch: %s", hipGetErrorString(err));
+    if (host_nparts) *host_nparts = nparts;
     return XSD_OK;
 }
 

@@ -145,6 +145,7 @@ def load():
     L.xsd_test_conv3x3_ex.argtypes = [vp, ctypes.POINTER(vp), i32, i32, fp, fp, ctypes.POINTER(XsdTestOut), i32, i32, ctypes.POINTER(f32), i32, i32, i32, vp]
     L.xsd_test_wgrad_ex.argtypes = [vp, ctypes.POINTER(vp), i32, ctypes.POINTER(vp), i32, i32, f32, i32, i32, i32, i32, i32, i32, fp, fp, i32, i32, i32, vp]
     ip = ctypes.POINTER(i32)
+    L.xsd_test_wgrad_block.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), f32, fp, ctypes.POINTER(i64), ctypes.POINTER(i64), i32, i32, ip, i32, i32, i32, vp]
     L.xsd_test_edge_expand.argtypes = [vp, fp, i64, fp, i32, i32, i32, fp, fp, fp, f32, vp, i32, fp, i32, i32, i32, vp]
     L.xsd_test_edge_reduce.argtypes = [vp, fp, fp, i32, i32, i32, fp, fp, i64, fp, fp, i64, i32, fp, i32, i32, i32, vp]
     L.xsd_test_edge_wgrad.argtypes = [vp, fp, fp, i64, i32, fp, fp, i32, i32, ip, i32, i32, i32, vp]
@@ -233,7 +234,7 @@ ABI_SYMBOLS = [
     "xsd_last_error", "xsd_version", "xsd_create", "xsd_destroy", "xsd_param_count", "xsd_set_math", "xsd_get_math", "xsd_pack_weights",
     "xsd_forward", "xsd_backward", "xsd_backward_num_stages", "xsd_backward_stage", "xsd_grad_range",
     "xsd_l1_loss", "xsd_loss_create", "xsd_loss_destroy", "xsd_loss_eval", "xsd_loss_set_channels", "xsd_ext_metrics_create", "xsd_ext_metrics_destroy", "xsd_ext_metrics_eval", "xsd_ext_metrics_test_stage", "xsd_fsim_create", "xsd_fsim_destroy", "xsd_fsim_eval", "xsd_fsim_test_dft2", "xsd_fsim_test_median", "xsd_fsim_test_stage", "xsd_adam_step", "xsd_mask_pad_normalize", "xsd_compose_input", "xsd_compose_batch", "xsd_normalize", "xsd_image_upsample",
-    "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd", "xsd_test_conv3x3_ex", "xsd_test_wgrad_ex",
+    "xsd_profile_enable", "xsd_profile_read", "xsd_probe_mfma_stream", "xsd_debug_stamps", "xsd_debug_persistent_grid", "xsd_debug_occupancy", "xsd_debug_residency_ms", "xsd_test_conv3x3", "xsd_test_conv3x3_bwd", "xsd_test_conv3x3_ex", "xsd_test_wgrad_ex", "xsd_test_wgrad_block",
     "xsd_test_edge_expand", "xsd_test_edge_reduce", "xsd_test_edge_wgrad", "xsd_test_gconv", "xsd_test_gwgrad", "xsd_test_gop", "xsd_test_gpack",
     "xsd_loss_test_scale", "xsd_loss_test_pool2", "xsd_test_clamp_bwd", "xsd_test_packed_region", "xsd_test_pad_gather", "xsd_test_add_channels",
     "xsd_restormer_create", "xsd_restormer_destroy", "xsd_restormer_param_count", "xsd_restormer_pack_weights", "xsd_restormer_forward",
