@@ -721,7 +721,9 @@ def test_max_abs_slot_array_grows_without_changing_results(tmp_path):
     """f16x3 scales every operand tensor from a max-|x| slot; the slot array grows (synchronize, reallocate, copy the packed
     panels' two slots, rebuild the plan) when the sizing pass counts more slots than are allocated -- 65,536 by default, i.e.
     only for nets like 256 filters x 64 blocks.  XSD_TEST_AMAX_CAP=128 (include/xsd.h) makes the 4-block shipped net take that
-    path, twice over (forward-only plan, then the training plan): outputs and gradients bit-equal to the default capacity."""
+    path, twice over (forward-only plan, then the training plan): outputs and gradients bit-equal to the default capacity.
+    Each process then repeats the run with a fresh module on a side stream behind a delay, the inputs written late: the growth
+    (stream 0) happens right before launches on a non-blocking stream, and the results are the default stream's bit for bit."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -738,6 +740,23 @@ def test_max_abs_slot_array_grows_without_changing_results(tmp_path):
         "y = m(xg); loss = (y - t).abs().mean(); loss.backward()\n"
         "g = {k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters()}\n"
         "g['dx'] = xg.grad.detach().cpu().numpy(); g['y0'] = y0; g['y'] = y.detach().cpu().numpy()\n"
+        # the same on a fresh module (its own engine: the slot array grows again) issued on a side stream behind a delay, with the
+        # inputs written late: the array is reallocated, zeroed and refilled on stream 0 right before launches on a non-blocking stream
+        "torch.manual_seed(9)\n"
+        "m2 = GeneratorRRDB_DN(1, 1, 32, 4).cuda().set_math('f16x3')\n"
+        "xl = (x * 55).requires_grad_(True); tl = t * 0.5\n"
+        "torch.cuda.synchronize()\n"
+        "side, end = torch.cuda.Stream(), torch.cuda.Event()\n"
+        "with torch.cuda.stream(side):\n"
+        "    torch.cuda._sleep(20000000); end.record()\n"
+        "    with torch.no_grad(): xl.copy_(x, non_blocking=True); tl.copy_(t, non_blocking=True)\n"
+        "    spinning = not end.query()\n"
+        "    with torch.no_grad(): y0s = m2(xl.detach())\n"
+        "    ys = m2(xl); ((ys - tl).abs().mean()).backward()\n"
+        "side.synchronize(); torch.cuda.synchronize()\n"
+        "for k, p in m2.named_parameters(): g['side.' + k] = p.grad.detach().cpu().numpy()\n"
+        "g['side.dx'] = xl.grad.detach().cpu().numpy(); g['side.y0'] = y0s.cpu().numpy(); g['side.y'] = ys.detach().cpu().numpy()\n"
+        "g['delay_still_running_before_the_call'] = np.array(spinning)\n"
         "np.savez(sys.argv[2], **g)\n")
     hooks = os.path.join(root, "xmm-superres-denoise_amd", "lib", "libxsd_hip_hooks.so")      # the only build that reads the variable (round 6)
     assert os.path.exists(hooks), "build the hooks variant: make -C xmm-superres-denoise_amd/csrc hooks"
@@ -755,6 +774,11 @@ def test_max_abs_slot_array_grows_without_changing_results(tmp_path):
     assert np.abs(a["y"]).max() > 0 and np.abs(a["conv_first.weight"]).max() > 0
     for k in a.files:
         assert np.array_equal(a[k], b[k]), k
+    for z in (a, b):       # the side-stream run of each process equals its default-stream run (and so each other's)
+        assert bool(z["delay_still_running_before_the_call"]), "delay too short: the side stream was idle when the module was called"
+        for k in z.files:
+            if k.startswith("side."):
+                assert np.array_equal(z[k], z[k[5:]]), k
 
 
 def test_second_backward_after_one_forward_starts_from_clean_max_slots():

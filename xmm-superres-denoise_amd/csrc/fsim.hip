@@ -465,6 +465,7 @@ int upload(void** dst, const void* src, size_t bytes)
 {
     if (hipMalloc(dst, bytes) != hipSuccess) { *dst = nullptr; return fail(XSD_ERR_NOMEM, "xsd_fsim: plan allocation of %zu bytes failed", bytes); }
     FSIM_HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    FSIM_HIPCHK(hipDeviceSynchronize());      // stream 0's upload is on the device before the eval's launches on a non-blocking stream read the plan
     return XSD_OK;
 }
 

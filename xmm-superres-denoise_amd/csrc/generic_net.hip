@@ -540,7 +540,8 @@ static bool gtable_alloc(GenericNet* n, const GTable& t)
            hipMalloc((void**)&n->descs_dev, sizeof(GPackDesc) * t.d.size()) == hipSuccess &&
            hipMemcpy(n->descs_dev, t.d.data(), sizeof(GPackDesc) * t.d.size(), hipMemcpyHostToDevice) == hipSuccess &&
            hipMalloc((void**)&n->wg_partial, sizeof(float) * (size_t)GenericNet::MAX_PARTS * maxw) == hipSuccess &&
-           hipMalloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) == hipSuccess;   // parts * cout <= capacity / (9 cin)
+           hipMalloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) == hipSuccess &&   // parts * cout <= capacity / (9 cin)
+           hipDeviceSynchronize() == hipSuccess;      // the descriptors (stream 0) are on the device before a pack on a non-blocking stream reads them
 }
 
 GenericNet* GenericNet::create(const xsd_config& cfg)

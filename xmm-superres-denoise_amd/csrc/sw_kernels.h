@@ -545,7 +545,8 @@ int alloc_weights(SwBase* r, const char* net, const std::vector<float>& mean)
 {
     if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
         hipMalloc((void**)&r->mean, sizeof(float) * mean.size()) != hipSuccess ||
-        hipMemcpy(r->mean, mean.data(), sizeof(float) * mean.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(r->mean, mean.data(), sizeof(float) * mean.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {      // (stream 0's upload is on the device before a forward on a non-blocking stream reads it)
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "%s: packed-weight allocation failed", net);
     }

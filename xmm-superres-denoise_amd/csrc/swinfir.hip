@@ -125,7 +125,9 @@ int set_twiddles(xsd_swinfir* r, int H, int W)
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "SwinFIR: twiddle table allocation failed");
     }
-    if (hipMemcpy(r->tw, t.data(), sizeof(float2) * t.size(), hipMemcpyHostToDevice) != hipSuccess)
+    // the upload goes to stream 0, the FFT passes that read the table to the caller's stream, which stream 0 does not order when it is
+    // non-blocking: the table is on the device before the passes are enqueued
+    if (hipMemcpy(r->tw, t.data(), sizeof(float2) * t.size(), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return rfail(XSD_ERR_HIP, "SwinFIR: twiddle table upload failed");
     r->twH = H; r->twW = W;
     return XSD_OK;

@@ -395,7 +395,7 @@ int xsd_swinir_test_pad(const float* dev_x, float* dev_y, int B, int C, int H, i
             (void)hipGetLastError();
             return rfail(XSD_ERR_NOMEM, "SwinIR pad test: allocation failed");
         }
-        if (hipMemcpy(dmean, mean, sizeof(float) * C, hipMemcpyHostToDevice) != hipSuccess) {
+        if (hipMemcpy(dmean, mean, sizeof(float) * C, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // on the device before the kernel on `s` reads it
             hipFree(dmean);
             return rfail(XSD_ERR_HIP, "SwinIR pad test: upload of the mean failed");
         }

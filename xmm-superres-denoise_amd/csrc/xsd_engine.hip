@@ -943,6 +943,11 @@ static int ensure_plan(xsd_engine* e, int B, int H, int W, bool train)
             if (err != hipSuccess) { hipFree(grown); return fail(XSD_ERR_HIP, "max-|x| slot copy failed: %s", hipGetErrorString(err)); }
             hipFree(e->amax);
         }
+        // hipMemset / hipMemcpy above run on stream 0, the launches that read the slots on the caller's stream, which may be non-blocking
+        // (no implicit order with stream 0); neither call is documented to have completed on the device when it returns (a memset of
+        // device memory may be asynchronous to the host; hipFree's implicit device synchronize runs only when there was an old array)
+        err = hipDeviceSynchronize();
+        if (err != hipSuccess) { hipFree(grown); e->amax = nullptr; e->amax_cap = 0; return fail(XSD_ERR_HIP, "max-|x| slot array: %s", hipGetErrorString(err)); }
         e->amax = grown; e->amax_cap = cap;
     }
     e->amax_used = 2;
@@ -1113,6 +1118,9 @@ int xsd_create(const xsd_config* cfg, xsd_engine** out)
     CK(hipMalloc((void**)&e->wg_bias_partial, sizeof(float) * (size_t)e->nparts * 4 * 32));
     CK(hipMalloc((void**)&e->edge_partial, sizeof(float) * EDGE_WGRAD_BLOCKS * 321));
     CK(hipMalloc((void**)&e->loss_partial, sizeof(double) * 1024));
+    // the hipMemset / hipMemcpy above went to stream 0; the first pack and forward may come on a non-blocking stream, which stream 0 does
+    // not order: what they read (zeroed slots, the zero page, the descriptors) is on the device before create returns
+    CK(hipDeviceSynchronize());
 #undef CK
     *out = e;
     return XSD_OK;

@@ -52,7 +52,7 @@ class TrainableSwinFIR(TrainableSwin):
             raise XsdError(f"SwinFIR needs H and W that are multiples of the window size {m.window} (window_partition, "
                            f"modules.py); got {H} x {W}")
         self.last_drop_masks = []
-        mean = m.mean.to(device=x.device, dtype=x.dtype)
+        mean = self._mean_like(x)
         y = self._pixelshuffle_tail(self._features((x - mean) * m.img_range))      # each block's own window: the clamped case
         y = (y / m.img_range + mean).contiguous()
         return y.clamp(0.0, 1.0) if self.clamp else y

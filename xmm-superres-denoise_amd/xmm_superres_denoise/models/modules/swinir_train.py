@@ -54,6 +54,7 @@ class TrainableSwin(nn.Module):
         self.generator = generator
         self.clamp = bool(clamp)
         self.last_drop_masks = []
+        self._mean_dev = None
 
     # ---- the wrapped module's names --------------------------------------------------------------------------------
     def state_dict(self, *args, **kwargs):
@@ -67,7 +68,17 @@ class TrainableSwin(nn.Module):
         st = self.__dict__.copy()
         st["generator"] = None
         st["last_drop_masks"] = []
+        st["_mean_dev"] = None
         return st
+
+    def _mean_like(self, x: torch.Tensor) -> torch.Tensor:
+        """the wrapped module's per-channel mean (a host tensor, as in the reference) on x's device: uploaded once and kept.  An upload
+        per forward is a copy from pageable host memory, which holds the host until x's stream has drained: every training step would
+        wait for the device instead of running ahead of it."""
+        kept = getattr(self, "_mean_dev", None)
+        if kept is None or kept.device != x.device or kept.dtype != x.dtype:
+            kept = self._mean_dev = self.module.mean.to(device=x.device, dtype=x.dtype)
+        return kept
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def _drop(self, t: torch.Tensor, p: float) -> torch.Tensor:
@@ -157,7 +168,7 @@ class TrainableSwinIR(TrainableSwin):
         self.last_drop_masks = []
         ph, pw = m._pads(H0, W0)
         up = m.upscale
-        mean = m.mean.to(device=x.device, dtype=x.dtype)
+        mean = self._mean_like(x)
         x = F.pad(x, (0, pw, 0, ph), "reflect") if ph or pw else x
         x = (x - mean) * m.img_range
         img = self._features(x, m.window)
