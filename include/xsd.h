@@ -13,6 +13,19 @@
  *   conv_last.*, and for SR: upsampling.{3u}.* (u<num_upsample), HRconv.*
  *   (xmm_superres_denoise/models/modules/generator_rrdb.py:10-64,73-101; rrdb_blocks.py:23-32,60-64).
  * Images are NCHW fp32: x [B][in_channels][H][W], y [B][out_channels][sH][sW] (the shipped models have one channel: plain [B][H][W]).
+ *
+ * This file is also read by a program: xmm_superres_denoise/engine/_lib.py derives the Python (ctypes) binding from it at import,
+ * after stripping comments and preprocessor lines.  The forms it accepts:
+ *   - `typedef struct xsd_X xsd_X;` (an opaque handle) and enums: skipped;
+ *   - `typedef struct xsd_X { ... } xsd_X;` with fields of the types below, fixed arrays of a literal length (`int32_t a[16]`) and several
+ *     declarators of one scalar type per statement (`double x, y;`);
+ *   - function declarations named xsd_*, over any number of lines, with named parameters of the types below or `(void)`, returning
+ *     one of the scalars, void or `const char*`;
+ *   - scalars: int, int32_t, int64_t, long long, float, double;
+ *   - pointers of any depth and constness to any named type: a single pointer to a struct defined above its use becomes a typed pointer
+ *     to the generated class, every other pointer (handles, `T**`, `const float* const*`, `void*`) an untyped address.
+ * Anything else -- another scalar type, a struct by value, an array or function-pointer parameter, a nested struct, a global -- makes
+ * the import fail and quote the declaration: extend the parser with the header, never around it.
  */
 #ifndef XSD_H
 #define XSD_H

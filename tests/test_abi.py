@@ -1,8 +1,8 @@
-"""CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol include/xsd.h declares,
+"""CPU-side checks of the drop-in boundary: the C-ABI library loads and exports exactly the entries include/xsd.h declares,
 the Python surface mirrors the reference's names, and the product path fails loudly without a GPU."""
 import ctypes
 import os
-import re
+import subprocess
 
 import pytest
 import torch
@@ -10,17 +10,21 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def exported_xsd_symbols(path):
+    """The defined dynamic symbols of a library whose names begin with xsd_."""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("xsd_")}
+
+
 def test_library_exports_every_declared_symbol():
+    """The entries the binding parsed from include/xsd.h are the library's exports: every declared entry is defined, and nothing
+    named xsd_* is exported that the header does not declare."""
     from xmm_superres_denoise.engine import _lib
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "xsd.h")).read()
-    declared = set(re.findall(r"\b(xsd_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_lib.ABI_SYMBOLS), declared ^ set(_lib.ABI_SYMBOLS)
-    for s in declared:
-        assert hasattr(L, s), s
-    L.xsd_version.restype = ctypes.c_char_p
+    declared, exported = set(_lib.ABI_SYMBOLS), exported_xsd_symbols(_lib.LIB_PATH)
+    assert declared == exported, declared ^ exported
+    L = _lib.bind(ctypes.CDLL(_lib.LIB_PATH))
     assert b"gfx950" in L.xsd_version()
 
 
@@ -156,7 +160,6 @@ def test_library_holds_only_the_adopted_conv_kernel_instances():
     """csrc/conv3x3_h2x.hip: X3_KINDS names the epilogue kinds that run on their own kernel instance; the others are not
     instantiated at all (no dead device code in the shipped library)."""
     import re
-    import subprocess
     from xmm_superres_denoise.engine import _lib
     src = open(os.path.join(_lib.CSRC_DIR, "conv3x3_h2x.hip")).read()
     kinds_mask = int(re.search(r"#define X3_KINDS (\d+)", src).group(1))
@@ -185,10 +188,8 @@ def test_product_library_reads_no_test_hook_from_the_environment():
     hb = open(hooks, "rb").read()
     for n in names:
         assert n in hb, n
-    L = ctypes.CDLL(hooks)
-    for s in _lib.ABI_SYMBOLS:
-        assert hasattr(L, s), s
-    L.xsd_version.restype = ctypes.c_char_p
+    assert exported_xsd_symbols(hooks) == set(_lib.ABI_SYMBOLS), exported_xsd_symbols(hooks) ^ set(_lib.ABI_SYMBOLS)
+    L = _lib.bind(ctypes.CDLL(hooks))
     assert b"test-hooks" in L.xsd_version()
 
 
@@ -198,9 +199,7 @@ def test_persistent_conv_grid_rule():
     arithmetic behind a diagnostic C-ABI entry: no device needed."""
     import ctypes
     from xmm_superres_denoise.engine import _lib
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    g = L.xsd_debug_persistent_grid
-    g.argtypes = [ctypes.c_int, ctypes.c_int]
+    g = _lib.bind(ctypes.CDLL(_lib.LIB_PATH)).xsd_debug_persistent_grid
     assert g(200, 256) == 200 and g(256, 256) == 256 and g(1, 256) == 1 and g(0, 256) == 0
     assert g(338, 256) == 169            # a 416 x 416 image (the reference's tile), batch 1: 169 x 2 instead of 82 x 2 + 174 x 1
     assert g(1352, 256) == 226           # batch 4 (the reference's training batch): 6 rounds on 226 workgroups

@@ -409,7 +409,6 @@ def test_refusals_write_nothing():
                 (np.array([0, 1]), None, np.array([n_slots, 0]))):
         rc, out = run_compose_batch(pool, idx, True, False, None, Hin, Win, 1, res)
         assert rc == ERR_ARG and np.isnan(out).all()
-        L.xsd_last_error.restype = ctypes.c_char_p
         assert b"sample" in L.xsd_last_error()
     # upsample < 1
     for s in (0, -2):

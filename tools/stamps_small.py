@@ -37,7 +37,6 @@ with torch.no_grad():
             m(x)
         torch.cuda.synchronize()
     if not os.environ.get("XSD_EXP_GRID") and hasattr(eng.L, "xsd_debug_persistent_grid"):      # the grid the launcher really uses (csrc/xsd_kernels.h: persistent_grid)
-        eng.L.xsd_debug_persistent_grid.argtypes = [ctypes.c_int, ctypes.c_int]
         nwg = int(eng.L.xsd_debug_persistent_grid(tiles, ncu))
     out = (ctypes.c_uint64 * 32)()
     eng.L.xsd_debug_stamps(eng.h, 1, None)

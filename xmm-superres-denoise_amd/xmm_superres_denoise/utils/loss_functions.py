@@ -15,7 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from ..config.config import LossCfg
-from ..engine._lib import XsdError, check, load
+from ..engine._lib import XsdError, XsdLossConfig as _LossConfigC, check, load      # xsd_loss_config, generated from include/xsd.h
 from ..engine.engine import _require_cuda_f32, _stream_ptr
 
 TERMS = ("l1", "poisson", "psnr", "ssim", "ms_ssim")
@@ -38,12 +38,6 @@ LOSS_TOML = {
                 "ms_ssim": (-2.043318348998774, 1.6309767061708214)},
     },
 }
-
-
-class _LossConfigC(ctypes.Structure):
-    _fields_ = [("w_l1", ctypes.c_float), ("w_poisson", ctypes.c_float), ("w_psnr", ctypes.c_float),
-                ("w_ssim", ctypes.c_float), ("w_ms_ssim", ctypes.c_float), ("correction", ctypes.c_float),
-                ("sigma", ctypes.c_float), ("k1", ctypes.c_float), ("k2", ctypes.c_float), ("kernel_size", ctypes.c_int32)]
 
 
 def load_loss_config(scaling: str = "linear", **overrides):
