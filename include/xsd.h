@@ -681,7 +681,9 @@ int xsd_debug_occupancy(int lds_bytes);
  * (a census of how many such workgroups are resident at once). */
 float xsd_debug_residency_ms(int grid, int threads, int lds_bytes, int us);
 
-/* Single-layer entry points used by the kernel-level parity tests (one 3x3 conv over NHWC 32-channel planes).
+/* Every xsd_test_* / xsd_loss_test_* entry from here on is defined in csrc/xsd_test_entries.hip, one object in the product and the
+ * test-hooks library alike, and calls the functions the engine calls (csrc/xsd_engine_impl.h).
+ * Single-layer entry points used by the kernel-level parity tests (one 3x3 conv over NHWC 32-channel planes).
  * dev_in: [n_in] plane pointers on the host (each plane [B][H][W][32]); w_oihw: device OIHW [32*n_out][32*n_in][3][3]. */
 int xsd_test_conv3x3(xsd_engine* e, const float* const* host_in_planes, int n_in, const float* dev_w_oihw, const float* dev_bias,
                      float* const* host_out_planes, int n_out, float slope, int B, int H, int W, void* stream);

@@ -21,32 +21,20 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <string>
 
 #include "../../include/xsd.h"
 
-namespace xsd {
-int set_last_error(int code, const std::string& msg);     // xsd_engine.hip: the thread-local message of xsd_last_error()
-}
+#include "xsd_err.h"
+#define fail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
 
 constexpr int TW = 64, TH = 4, NT = TW * TH;      // one workgroup = a 64 x 4 tile of a map = four waves, one per row
 constexpr int NSCALE = 4;
 constexpr int VIF_TAPS[NSCALE] = {17, 9, 5, 3};   // n = 2^(4-s) + 1
-
-static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return xsd::set_last_error(code, buf);
-}
 
 struct Plane {            // one image level: B images of h x w, x (preds) and y (target)
     const float* x;

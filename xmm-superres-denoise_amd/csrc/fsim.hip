@@ -24,7 +24,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <new>
 #include <string>
@@ -32,9 +31,8 @@
 
 #include "../../include/xsd.h"
 
-namespace xsd {
-int set_last_error(int code, const std::string& msg);     // xsd_engine.hip: the thread-local message of xsd_last_error()
-}
+#include "xsd_err.h"
+#define fail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
 
@@ -42,16 +40,6 @@ constexpr int TW = 64, TH = 4, NT = TW * TH;      // pointwise kernels: one work
 constexpr int NO = 4, NS = 4, NF = NO * NS;       // orientations, scales, filters (index o * NS + s)
 constexpr int MAX_SIDE = 1024;
 constexpr double PI = 3.14159265358979323846;
-
-static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return xsd::set_last_error(code, buf);
-}
 
 // ---- the complex GEMM:  C[bt][m][n] = scale * sum_k A[bt][m][k] * B[bt][k][n]
 enum { K_CF32 = 1, K_CF64 = 2, K_RF64 = 3 };

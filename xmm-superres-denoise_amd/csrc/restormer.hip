@@ -31,28 +31,16 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../include/xsd.h"
 
-namespace xsd {
-int set_last_error(int code, const std::string& msg);     // xsd_engine.hip: the thread-local message of xsd_last_error()
-}
+#include "xsd_err.h"
+#define rfail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
-
-int rfail(int code, const char* fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return xsd::set_last_error(code, buf);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // kernels

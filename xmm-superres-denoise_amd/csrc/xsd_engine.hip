@@ -1,5 +1,5 @@
 // xsd_engine.hip -- host side of the engine: network plan (forward / backward launch schedules over feature planes),
-// workspace, weight packing, and the C ABI declared in include/xsd.h.
+// workspace, weight packing, and the C ABI declared in include/xsd.h (its kernel-level test entries: xsd_test_entries.hip, over xsd_engine_impl.h).
 //
 // The schedule restates, layer by layer, the reference graph
 //   _GeneratorRRDB.forward / GeneratorRRDB_SR.forward / GeneratorRRDB_DN.forward (generator_rrdb.py:66-69,103-110,130-137)
@@ -22,15 +22,10 @@
 #include <new>
 #include <vector>
 
-#include "../../include/xsd.h"
-#include "xsd_aux.h"
-#include "generic_net.h"
 #include "xsd_loss.h"
+#include "xsd_engine_impl.h"
 
 static constexpr int EDGE_WGRAD_BLOCKS = 2048; // 8 workgroups of 256 threads per CU
-#include "xsd_kernels.h"
-
-using namespace xsd;
 
 namespace xsd {
 int debug_conv_occupancy(int lds_bytes);
@@ -40,7 +35,8 @@ hipError_t launch_pack_shuffle_bias(const float* b, float* out, int planes, hipS
 }
 
 static thread_local std::string g_err;
-static int fail(int code, const char* fmt, ...)
+namespace xsd {
+int failf(int code, const char* fmt, ...)      // xsd_err.h: every translation unit of the library reports through here
 {
     char buf[1024];
     va_list ap;
@@ -50,102 +46,7 @@ static int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
-namespace xsd {
-int set_last_error(int code, const std::string& msg)      // for the other translation units of the library (restormer.hip)
-{
-    g_err = msg;
-    return code;
-}
 } // namespace xsd
-#define HIPCHK(expr)                                                                                      \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) return fail(XSD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-
-struct ConvW {       // one MFMA conv's weights
-    long long w_off, b_off; // flat-param offsets
-    int cout, cin, shuffle;
-    long long fwd_off, bwd_off; // packed offsets (floats)
-    long long sbias_off;        // shuffled-bias offset (shuffle convs) or -1
-    float bwd_scale = 1.f;      // folded into the input-gradient panels
-};
-
-typedef std::function<hipError_t(hipStream_t)> Launch;
-
-struct ProfRec { hipEvent_t a, b; double flop, bytes; int klass; };
-
-struct xsd_engine {
-    xsd_config cfg;
-    GenericNet* generic = nullptr;   // what the plane kernels do not take (generic_net.hip): more than 256 filters, more than 8 image channels
-    // Widths that are no multiple of 32 run zero-padded to the next one: the engine is built for `nf_pad` filters over an internal,
-    // padded flat parameter vector (pad weights and biases 0 -> pad channels are exactly 0 everywhere, forward and backward); the
-    // caller's vectors keep the reference's layout for `cfg.num_filters` (pad_params_kernel expands, pad_grads_kernel gathers)
-    int nf_pad = 0;                  // 0: no padding
-    long long nparams_pad = 0;
-    float* params_pad = nullptr;
-    float* grads_pad = nullptr;
-    void* pad_descs = nullptr;       // PadDesc[npad]: first | dense blocks | trunk, last, up.., hr  (= backward stages last | 1..blocks | 0)
-    int npad = 0;
-    std::vector<long long> rrdb_begin_real;
-    long long nparams_real = 0;
-    int planes = 1;                  // num_filters / 32: 32-channel planes per feature tensor (1 = the shipped configuration; up to 8: Builder::build)
-    long long nparams = 0;
-    // flat-param offsets
-    long long first_w = 0, first_b = 0, last_w = 0, last_b = 0;
-    std::vector<ConvW> rdb; // blocks*15
-    ConvW trunk, hr;
-    std::vector<ConvW> up;
-    std::vector<long long> rrdb_begin; // flat offset where rrdb.i starts; [blocks] = trunk offset
-    // packed weights
-    float* pk_fwd = nullptr;
-    float* pk_bwd = nullptr;
-    unsigned short* pk_fwd_s = nullptr; // split-mode panels (mode 3: fp32 in bf16-MFMA fragment order; mode 4: two-term fp16 images),
-    unsigned short* pk_bwd_s = nullptr; // same byte size / offsets as pk_fwd / pk_bwd
-    int chunk = 0;             // diagnostic library only (env XSD_CHUNK): images per dense-block sweep (0 = whole batch)
-    int ablate = 0;            // diagnostic library only (env XSD_ABLATE): ablation knobs of the kernels
-    int math = 4;              // include/xsd.h: xsd_set_math (default: f16x3, the faster of the two fp32-class split modes)
-    float* pk_edge = nullptr; // first_fwd, first_bwd, last_fwd, last_bwd (288 each)
-    float* pk_sbias = nullptr;
-    PackDesc* descs_dev = nullptr;
-    int ndesc = 0;
-    long long pk_floats = 0;
-    // math mode 4 (f16x3): max |x| slots; [0] packed forward panels, [1] packed input-gradient panels, [2..] planes of the plan
-    float* amax = nullptr;
-    int amax_used = 2;
-    int amax_bwd_first = 2;    // first slot the plan hands out while it builds the BACKWARD stages (re-zeroed by stage 0 of every backward)
-    int ncu = 256;             // compute units of the device the engine was created on (the weight gradient's block launch is dealt from it)
-    int amax_cap = 65536;      // floats allocated behind `amax`; ensure_plan grows it to what the plan's sizing pass counted (+ AMAX_TAIL)
-    static constexpr int AMAX_TAIL = 64;   // the last slots belong to the single-conv entry points (pack_single, the weight-gradient hook)
-    const float* params = nullptr; // borrowed (bias reads)
-    bool packed = false;
-    // workspace
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    float* wg_partial = nullptr;
-    float* wg_bias_partial = nullptr;
-    float* edge_partial = nullptr;
-    double* loss_partial = nullptr;
-    int nparts = 256;
-    // plan
-    int pB = 0, pH = 0, pW = 0, ptrain = -1;
-    std::vector<Launch> fwd_ops;
-    std::vector<std::vector<Launch>> bwd_stages;
-    bool fwd_saved = false;
-    // late-bound call pointers
-    const float* b_x = nullptr;
-    float* b_y = nullptr;
-    const float* b_dy = nullptr;
-    float* b_dx = nullptr;
-    float* b_grads = nullptr;
-    void* zero_page = nullptr;         // 256 B of zeros (padding source of the DMA / unconditional loads) + 256 B of trash
-    unsigned long long* dbg = nullptr; // conv phase stamps (diagnostic)
-    // profiling
-    bool prof = false;
-    std::vector<ProfRec> recs;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-};
 
 // ------------------------------------------------------------------------------------------------------------
 static void take_conv(long long& off, int cout, int cin, long long& w, long long& b)
@@ -156,14 +57,14 @@ static void take_conv(long long& off, int cout, int cin, long long& w, long long
 
 // weight gradient of the split modes: mode 3 (bf16x6) and mode 4 (f16x3) have their own role-split kernels (one workgroup
 // per CU, `nparts` partial sums); diagnostic ablate bit 22 runs mode 3's kernel in mode 4
-static hipError_t launch_wgrad_split(int math, int ablate, const WgradParams& p, hipStream_t s)
+hipError_t launch_wgrad_split(int math, int ablate, const WgradParams& p, hipStream_t s)
 {
     return (math == 4 && !(ablate & (1 << 22))) ? launch_wgrad_h2x(p, s) : launch_wgrad_s3x(p, s);
 }
 
 // Parts (partial sums) of one weight-gradient launch over the n_in x n_g rectangle: the plan (Builder::wgrad_launch) and the single-launch
 // test hook (xsd_test_wgrad_ex) both ask here, so the hook cannot drift from the plan.
-static int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
+int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
 {
 #ifndef XSD_WGRAD_ROUNDS
     // The grid is nparts x n_in x n_g workgroups of one per CU: with nparts = the CU count a launch over k (X, G) pairs runs k
@@ -184,7 +85,7 @@ static int wgrad_nparts(const xsd_engine* e, int n_in, int n_g)
 // m parts per XCD, each 15 workgroups side by side: m = CUs / (8 x 15), at most 10 ((8 m + 1) x 15 partial panels must fit
 // wg_partial's 256 x 5); m = 0 (fewer than 120 CUs): the plan runs one launch per G instead
 static int block_parts_per_xcd(int ncu) { const int m = ncu / 120; return m > 10 ? 10 : m; }
-static int wgrad_block_nparts(const xsd_engine* e)
+int wgrad_block_nparts(const xsd_engine* e)
 {
     // (MI355X: 256 CUs -> 16 parts = 240 workgroups; the kernel's decode takes any nparts = 8 m or 8 m + 1)
     const int m = block_parts_per_xcd(e->ncu);
@@ -198,12 +99,8 @@ static int wgrad_block_nparts(const xsd_engine* e)
 #endif
     return (tail && e->ncu - 120 * m >= 16) ? 8 * m + 1 : 8 * m;
 }
-struct WgradBlock {
-    WgradParams wp;               // the pair-list launch; the caller sets the planes, their max-|x| slots and the late-bound pointers
-    WgradReduceParams rp[5];      // conv n + 1's reduction; the caller sets dw and db
-};
 // `k.wp` comes from Builder::wgrad_base; cin[n], cout[n]: the OIHW extent of conv n + 1's gradient; gscale: conv 5's factor
-static void wgrad_block_fill(WgradBlock& k, int nparts, const int cin[5], const int cout[5], float gscale, float* partial, float* bias_partial)
+void wgrad_block_fill(WgradBlock& k, int nparts, const int cin[5], const int cout[5], float gscale, float* partial, float* bias_partial)
 {
     WgradParams& wp = k.wp;
     wp.n_in = 5; wp.n_g = 5; wp.nparts = nparts; wp.npairs = 15;
@@ -225,7 +122,7 @@ static void wgrad_block_fill(WgradBlock& k, int nparts, const int cin[5], const 
     }
 }
 // the five convs' fixed-order reductions as one launch (bitwise what five launches give: `separate`, the test hook's other form)
-static hipError_t wgrad_block_reduce(const WgradBlock& k, bool separate, hipStream_t s)
+hipError_t wgrad_block_reduce(const WgradBlock& k, bool separate, hipStream_t s)
 {
     if (separate) {
         for (int n = 0; n < 5; ++n) { hipError_t err = launch_wgrad_reduce(k.rp[n], s); if (err != hipSuccess) return err; }
@@ -240,12 +137,8 @@ static hipError_t wgrad_block_reduce(const WgradBlock& k, bool separate, hipStre
 
 // Workgroups (partial sums) of one edge weight-gradient launch: the plan and the single-launch test hook (xsd_test_edge_wgrad) both ask
 // here.  A constant: the kernel strides over the image rows, idle workgroups store zeros, edge_partial holds this many records.
-static int edge_wgrad_nblocks() { return EDGE_WGRAD_BLOCKS; }
+int edge_wgrad_nblocks() { return EDGE_WGRAD_BLOCKS; }
 
-// Profile classes of xsd_profile_read (include/xsd.h): 0 conv (forward + input-gradient), 1 weight gradient; the HBM-bound kernels:
-// 2 edge_expand (1 -> 32), 3 edge_reduce (32 -> 1), 4 edge_wgrad, 5 L1 loss, 6 Adam, 7 clamp backward, 8 plane max |x| sweeps.
-// `bytes` is ALGORITHMIC traffic (SURVEY 8d rule: every operand once), `flop` 2 x MAC.
-enum { PK_CONV = 0, PK_WGRAD = 1, PK_EDGE_EXPAND = 2, PK_EDGE_REDUCE = 3, PK_EDGE_WGRAD = 4, PK_LOSS = 5, PK_ADAM = 6, PK_CLAMP_BWD = 7, PK_PLANE_AMAX = 8, PK_COUNT = 9 };
 static hipError_t prof_launch(xsd_engine* e, int klass, double flop, double bytes, hipStream_t s, const std::function<hipError_t()>& f)
 {
     if (!e->prof) return f();
@@ -267,7 +160,7 @@ static hipError_t prof_launch(xsd_engine* e, int klass, double flop, double byte
 }
 
 // conv launch of the engine's math mode (mode 4 also needs the weight buffers' max |w| slot: forward or input-gradient panels)
-static hipError_t launch_conv_any(xsd_engine* eng, ConvParams& p, hipStream_t s)
+hipError_t launch_conv_any(xsd_engine* eng, ConvParams& p, hipStream_t s)
 {
     if (eng->math == 4) {
         if (!p.amax_w) {
@@ -300,9 +193,8 @@ static hipError_t run_edge_wgrad(xsd_engine* e, const EdgeWgradParams& p, int wh
 // ------------------------------------------------------------------------------------------------------------
 // Plan builder
 // ------------------------------------------------------------------------------------------------------------
-struct Builder {
+struct Builder : PlaneViews {
     xsd_engine* e;
-    int B, H, W;
     bool train;
     uintptr_t base;      // 0 in the sizing pass
     size_t top = 0, peak = 0;
@@ -313,7 +205,7 @@ struct Builder {
     typedef std::tuple<uintptr_t, int, int> ViewKey;
     std::map<ViewKey, float*> amax_valid;
     Builder(xsd_engine* e_, int B_, int H_, int W_, bool train_, uintptr_t base_)
-        : e(e_), B(B_), H(H_), W(W_), train(train_), base(base_), freelist(8) {}
+        : PlaneViews{B_, H_, W_}, e(e_), train(train_), base(base_), freelist(8) {}
 
     float* new_slot()
     {
@@ -400,66 +292,6 @@ struct Builder {
     const float* bwdp(long long off) const
     {
         return e->math ? reinterpret_cast<const float*>(e->pk_bwd_s) + off : e->pk_bwd + off;
-    }
-    ConvParams conv_base(int level) const
-    {
-        ConvParams p;
-        memset(&p, 0, sizeof(p));
-        p.B = B; p.H = H << level; p.W = W << level;
-        p.tilesX = (p.W + TILE_W - 1) / TILE_W;
-        p.tilesY = (p.H + TILE_H - 1) / TILE_H;
-        p.std_rs = p.W * 32;
-        p.std_bs = (long long)p.H * p.W * 32;
-        for (int j = 0; j < 5; ++j) { p.out[j].a1 = 1.f; p.out[j].a2 = 1.f; p.out[j].slope = 1.f; p.out[j].mslope = 1.f; }
-        return p;
-    }
-    WgradParams wgrad_base(int level) const
-    {
-        WgradParams wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.B = B; wp.H = H << level; wp.W = W << level;
-        wp.tilesX = (wp.W + TILE_W - 1) / TILE_W;
-        wp.tilesY = (wp.H + TILE_H - 1) / TILE_H;
-        return wp;
-    }
-    PlaneIn std_in(const float* p, int level) const
-    {
-        PlaneIn r; r.p = p; r.ps = 32; r.rs = (W << level) * 32; r.bs = (long long)(H << level) * (W << level) * 32; return r;
-    }
-    // sub-pixel (i,j) view at `level` of a plane stored at level+1 (PixelShuffle(2), generator_rrdb.py:97)
-    PlaneIn shuf_in(const float* hr, int level, int n) const
-    {
-        const int Wl = W << level, Hl = H << level;
-        PlaneIn r; r.p = hr + ((long long)(n >> 1) * 2 * Wl + (n & 1)) * 32; r.ps = 64; r.rs = 4 * Wl * 32;
-        r.bs = (long long)4 * Hl * Wl * 32; return r;
-    }
-    void std_out(OutDesc& o, float* p, int level) const
-    {
-        o.p = p; o.ps = 32; o.rs = (W << level) * 32; o.bs = (long long)(H << level) * (W << level) * 32;
-    }
-    void shuf_out(OutDesc& o, float* hr, int level, int n) const
-    {
-        PlaneIn r = shuf_in(hr, level, n);
-        o.p = const_cast<float*>(r.p); o.ps = r.ps; o.rs = r.rs; o.bs = r.bs;
-    }
-
-    // the same conv restricted to images [b0, b0 + nb)
-    static ConvParams slice(const ConvParams& q, int b0, int nb)
-    {
-        ConvParams p = q;
-        p.B = nb;
-        for (int i = 0; i < 5; ++i) if (p.in[i].p) p.in[i].p += (long long)b0 * p.in[i].bs;
-        for (int j = 0; j < 5; ++j) {
-            OutDesc& o = p.out[j];
-            if (o.p) o.p += (long long)b0 * o.bs;
-            if (o.e1) o.e1 += (long long)b0 * p.std_bs;
-            if (o.e2) o.e2 += (long long)b0 * p.std_bs;
-            if (o.e3) o.e3 += (long long)b0 * p.std_bs;
-            if (o.mask) o.mask += (long long)b0 * p.std_bs;
-            if (o.bits_out) o.bits_out += (long long)b0 * (p.std_bs / 16);   // 2 half-words per pixel of 32 floats
-            if (o.bits_in) o.bits_in += (long long)b0 * (p.std_bs / 16);
-        }
-        return p;
     }
     Launch conv_launch(const ConvParams& p_in, bool bias_from_params, long long bias_off)
     {
@@ -961,11 +793,6 @@ static int ensure_plan(xsd_engine* e, int B, int H, int W, bool train)
 // ------------------------------------------------------------------------------------------------------------
 // zero-padded widths: expansion of the caller's parameters / gathering of the gradients
 // ------------------------------------------------------------------------------------------------------------
-struct PadDesc {
-    long long w_r, b_r, w_p, b_p;    // weight / bias offsets in the caller's (real) and in the padded flat vector
-    int cout_r, cin_r, cin_p;        // OIHW extents (cout_p never matters: output channel oc keeps its index)
-    int tin_r, tin_p;                // width of the tensors the input is concatenated from: input channel t*tin_r + k <-> t*tin_p + k
-};
 __global__ void pad_params_kernel(const float* real, float* padded, const PadDesc* descs, int to_real /* 0: expand params, 1: gather grads */)
 {
     const PadDesc d = descs[blockIdx.y];
@@ -979,6 +806,30 @@ __global__ void pad_params_kernel(const float* real, float* padded, const PadDes
         } else { r = d.b_r + (e - nw); q = d.b_p + (e - nw); }
         if (to_real) const_cast<float*>(real)[r] = padded[q]; else padded[q] = real[r];
     }
+}
+hipError_t launch_pad_params(const float* real, float* padded, const PadDesc* descs_dev, int ndesc, int to_real, hipStream_t s)
+{
+    hipLaunchKernelGGL(pad_params_kernel, dim3(64, ndesc), dim3(256), 0, s, real, padded, descs_dev, to_real);
+    return hipGetLastError();
+}
+
+// OIHW weights -> packed panels of math mode `math`, for the `ndesc` convs of a descriptor table: xsd_pack_weights with the engine's
+// buffers, the test entries' single-conv packer with its temporaries.  Mode 0 fills pk_fwd / pk_bwd, mode 3 pk_fwd_s / pk_bwd_s, mode 4
+// all four and the two max-|w| slots amax2[0] (forward panels), amax2[1] (input-gradient panels).
+hipError_t pack_panels(int math, const float* dev_params, const PackDesc* descs_dev, int ndesc, float* pk_fwd, float* pk_bwd,
+                       void* pk_fwd_s, void* pk_bwd_s, long long pk_floats, float* amax2, hipStream_t s)
+{
+    if (math == 3) return launch_pack_weights_s3(dev_params, descs_dev, ndesc, static_cast<float*>(pk_fwd_s), static_cast<float*>(pk_bwd_s), s);
+    if (math != 4) return launch_pack_weights(dev_params, descs_dev, ndesc, pk_fwd, pk_bwd, s);
+    // fp32 fragment-order panels into the (otherwise unused) mode-0 buffers, max |w| of the forward and of the
+    // input-gradient panels (one power-of-two scale each), then the two-term fp16 images the conv kernel copies to LDS
+    hipError_t err = launch_pack_weights_s3(dev_params, descs_dev, ndesc, pk_fwd, pk_bwd, s);
+    if (err == hipSuccess) err = hipMemsetAsync(amax2, 0, 2 * sizeof(float), s);
+    if (err == hipSuccess) err = launch_buffer_amax(pk_fwd, pk_floats, amax2 + 0, s);
+    if (err == hipSuccess) err = launch_buffer_amax(pk_bwd, pk_floats, amax2 + 1, s);
+    if (err == hipSuccess) err = launch_split_panels_f16(pk_fwd, pk_fwd_s, pk_floats, amax2 + 0, s);
+    if (err == hipSuccess) err = launch_split_panels_f16(pk_bwd, pk_bwd_s, pk_floats, amax2 + 1, s);
+    return err;
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1158,25 +1009,11 @@ int xsd_pack_weights(xsd_engine* e, const float* dev_params, void* stream)
     if (e->generic) { HIPCHK(e->generic->pack(dev_params, s)); e->packed = true; return XSD_OK; }
     if (e->nf_pad) {     // the engine runs on the zero-padded copy
         HIPCHK(hipMemsetAsync(e->params_pad, 0, sizeof(float) * e->nparams_pad, s));
-        hipLaunchKernelGGL(pad_params_kernel, dim3(64, e->npad), dim3(256), 0, s, dev_params, e->params_pad, static_cast<const PadDesc*>(e->pad_descs), 0);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_pad_params(dev_params, e->params_pad, static_cast<const PadDesc*>(e->pad_descs), e->npad, 0, s));
         dev_params = e->params_pad;
         e->params = dev_params;
     }
-    if (e->math == 4) {
-        // fp32 fragment-order panels into the (otherwise unused) mode-0 buffers, max |w| of the forward and of the
-        // input-gradient panels (one power-of-two scale each), then the two-term fp16 images the conv kernel copies to LDS
-        HIPCHK(launch_pack_weights_s3(dev_params, e->descs_dev, e->ndesc, e->pk_fwd, e->pk_bwd, s));
-        HIPCHK(hipMemsetAsync(e->amax, 0, 2 * sizeof(float), s));
-        HIPCHK(launch_buffer_amax(e->pk_fwd, e->pk_floats, e->amax + 0, s));
-        HIPCHK(launch_buffer_amax(e->pk_bwd, e->pk_floats, e->amax + 1, s));
-        HIPCHK(launch_split_panels_f16(e->pk_fwd, e->pk_fwd_s, e->pk_floats, e->amax + 0, s));
-        HIPCHK(launch_split_panels_f16(e->pk_bwd, e->pk_bwd_s, e->pk_floats, e->amax + 1, s));
-    } else if (e->math == 3) {
-        HIPCHK(launch_pack_weights_s3(dev_params, e->descs_dev, e->ndesc, reinterpret_cast<float*>(e->pk_fwd_s), reinterpret_cast<float*>(e->pk_bwd_s), s));
-    }
-    else
-        HIPCHK(launch_pack_weights(dev_params, e->descs_dev, e->ndesc, e->pk_fwd, e->pk_bwd, s));
+    HIPCHK(pack_panels(e->math, dev_params, e->descs_dev, e->ndesc, e->pk_fwd, e->pk_bwd, e->pk_fwd_s, e->pk_bwd_s, e->pk_floats, e->amax, s));
     {   // conv_first W[c][ch][tap] and conv_last W[co][c][tap], 32 feature channels (one plane) of one image channel at a time
         const int P = e->planes, ci = e->cfg.in_channels, co = e->cfg.out_channels, nf = 32 * P;
         float* ff = e->pk_edge; float* fb = ff + 288 * P * ci; float* lf = fb + 288 * P * ci; float* lb = lf + 288 * P * co;
@@ -1250,8 +1087,7 @@ int xsd_backward_stage(xsd_engine* e, int stage, const float* dev_dy, float* dev
         if (stage == blocks + 1) { d0 = 0; d1 = 1; }                                   // conv_first
         else if (stage >= 1) { const int i = blocks - stage; d0 = 1 + 15 * i; d1 = d0 + 15; }   // dense blocks of rrdb.i
         else { d0 = 1 + 15 * blocks; d1 = e->npad; }                                  // trunk, conv_last, upsampling, HRconv
-        hipLaunchKernelGGL(pad_params_kernel, dim3(64, d1 - d0), dim3(256), 0, s, dev_grads, e->grads_pad, static_cast<const PadDesc*>(e->pad_descs) + d0, 1);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_pad_params(dev_grads, e->grads_pad, static_cast<const PadDesc*>(e->pad_descs) + d0, d1 - d0, 1, s));
     }
     return XSD_OK;
 }
@@ -1338,7 +1174,7 @@ int xsd_loss_eval(xsd_loss_fn* f, const float* dev_y, const float* dev_target, f
     if (!f || !dev_y || !dev_target || !dev_out8) return fail(XSD_ERR_ARG, "bad argument");
     if (B < 1 || B % f->channels) return fail(XSD_ERR_ARG, "xsd_loss_eval: %d images are no whole number of %d-channel samples (xsd_loss_set_channels)", B, f->channels);
     const char* why = nullptr;
-    if (loss_check(f->w, B, H, W, &why)) return fail(XSD_ERR_ARG, why);
+    if (loss_check(f->w, B, H, W, &why)) return fail(XSD_ERR_ARG, "%s", why);
     const size_t need = loss_workspace_bytes(B, H, W);
     if (need > f->ws_bytes) {
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
@@ -1493,531 +1329,6 @@ int xsd_profile_read(xsd_engine* e, int klass, double* total_ms, int64_t* launch
     if (launches) *launches = n;
     if (total_flop) *total_flop = fl;
     if (total_bytes) *total_bytes = by;
-    return XSD_OK;
-}
-
-// ---- single-layer test hooks ---------------------------------------------------------------------------------
-static int pack_single(const float* dev_w, int cout, int cin, float** fwd, float** bwd, int math, hipStream_t s, float* amax_slots = nullptr)
-{
-    const long long n = (long long)(cout / 32) * (cin / 32) * PANEL_FLOATS;
-    PackDesc d; d.src_w = 0; d.dst_fwd = 0; d.dst_bwd = 0; d.cout = cout; d.cin = cin; d.shuffle = 0; d.bwd_scale = 1.f;
-    PackDesc* dd = nullptr;
-    HIPCHK(hipMalloc((void**)fwd, sizeof(float) * n));
-    HIPCHK(hipMalloc((void**)bwd, sizeof(float) * n));
-    HIPCHK(hipMalloc((void**)&dd, sizeof(PackDesc)));
-    HIPCHK(hipMemcpy(dd, &d, sizeof(d), hipMemcpyHostToDevice));
-    if (math == 4) {   // as xsd_pack_weights: fp32 panels -> max |w| (slots CAP-4 / CAP-3 of `amax`) -> two-term fp16 images
-        float *tf = nullptr, *tb = nullptr;
-        HIPCHK(hipMalloc((void**)&tf, sizeof(float) * n));
-        HIPCHK(hipMalloc((void**)&tb, sizeof(float) * n));
-        HIPCHK(launch_pack_weights_s3(dev_w, dd, 1, tf, tb, s));
-        HIPCHK(hipMemsetAsync(amax_slots, 0, 2 * sizeof(float), s));
-        HIPCHK(launch_buffer_amax(tf, n, amax_slots + 0, s));
-        HIPCHK(launch_buffer_amax(tb, n, amax_slots + 1, s));
-        HIPCHK(launch_split_panels_f16(tf, *fwd, n, amax_slots + 0, s));
-        HIPCHK(launch_split_panels_f16(tb, *bwd, n, amax_slots + 1, s));
-        HIPCHK(hipStreamSynchronize(s));
-        hipFree(tf); hipFree(tb);
-    } else if (math == 3) HIPCHK(launch_pack_weights_s3(dev_w, dd, 1, *fwd, *bwd, s));
-    else HIPCHK(launch_pack_weights(dev_w, dd, 1, *fwd, *bwd, s));
-    HIPCHK(hipStreamSynchronize(s));
-    hipFree(dd);
-    return XSD_OK;
-}
-
-static hipError_t run_conv(xsd_engine* e, ConvParams& p, hipStream_t s)
-{
-    p.zero = e->zero_page;
-    p.ablate = e->ablate;      // (0 outside the diagnostic library)
-    for (int i = 0; i < (p.n_out > 1 ? p.n_out : p.n_in); ++i) p.wstep[i] = p.wpanel + (long long)i * PANEL_FLOATS;
-    if (e->math == 4) {   // test hook: nobody has reported the operands' max |x| -> reduce them here (slots at the end of the array)
-        float* t = e->amax + e->amax_cap - 32;    // (CAP-16.. belong to the weight-gradient hook, CAP-4 / CAP-3 to pack_single)
-        hipError_t err = hipMemsetAsync(t, 0, 8 * sizeof(float), s);
-        if (err != hipSuccess) return err;
-        for (int i = 0; i < p.n_in; ++i) {
-            err = launch_plane_amax(p.in[i], p.B, p.H, p.W, t + i, s);
-            if (err != hipSuccess) return err;
-            p.amax_in[i] = t + i;
-        }
-        if (!p.amax_w) return hipErrorInvalidValue;   // set by the hook from pack_single's slots (forward or input-gradient panels)
-        return launch_conv3x3_h2x(p, s);
-    }
-    if (e->math == 3) return launch_conv3x3_s3x(p, s);
-    return launch_conv3x3_mfma(p, s);
-}
-
-int xsd_test_conv3x3(xsd_engine* e, const float* const* in_planes, int n_in, const float* dev_w_oihw, const float* dev_bias,
-                     float* const* out_planes, int n_out, float slope, int B, int H, int W, void* stream)
-{
-    if (!e || n_in < 1 || n_in > 5 || n_out < 1 || n_out > 5 || (n_in > 1 && n_out > 1)) return fail(XSD_ERR_ARG, "bad n_in/n_out");
-    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
-    hipStream_t s = (hipStream_t)stream;
-    float *fwd = nullptr, *bwd = nullptr;
-    int rc = pack_single(dev_w_oihw, 32 * n_out, 32 * n_in, &fwd, &bwd, e->math, s, e->amax + e->amax_cap - 4);
-    if (rc) return rc;
-    Builder b(e, B, H, W, false, 0);
-    ConvParams p = b.conv_base(0);
-    p.n_in = n_in; p.n_out = n_out; p.wpanel = fwd; p.bias = dev_bias;
-    p.amax_w = e->amax + e->amax_cap - 4;     // mode 4: max |w| of the forward panels (pack_single)
-    for (int i = 0; i < n_in; ++i) p.in[i] = b.std_in(in_planes[i], 0);
-    for (int j = 0; j < n_out; ++j) { b.std_out(p.out[j], out_planes[j], 0); p.out[j].slope = slope; }
-    hipError_t err = run_conv(e, p, s);
-    hipStreamSynchronize(s);
-    hipFree(fwd); hipFree(bwd);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "conv launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_conv3x3_bwd(xsd_engine* e, const float* const* in_planes, int n_in, const float* dev_w_oihw, const float* dev_g_plane,
-                         float* const* dx_planes, float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream)
-{
-    if (!e || n_in < 1 || n_in > 5) return fail(XSD_ERR_ARG, "bad n_in");
-    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
-    hipStream_t s = (hipStream_t)stream;
-    float *fwd = nullptr, *bwd = nullptr;
-    int rc = pack_single(dev_w_oihw, 32, 32 * n_in, &fwd, &bwd, e->math, s, e->amax + e->amax_cap - 4);
-    if (rc) return rc;
-    const float* g = dev_g_plane;
-    Builder b(e, B, H, W, false, 0);
-    ConvParams p = b.conv_base(0);
-    p.n_in = 1; p.n_out = n_in; p.wpanel = bwd; p.in[0] = b.std_in(g, 0);
-    p.amax_w = e->amax + e->amax_cap - 3;     // mode 4: max |w| of the input-gradient panels
-    for (int j = 0; j < n_in; ++j) b.std_out(p.out[j], dx_planes[j], 0);
-    hipError_t err = run_conv(e, p, s);
-    if (err == hipSuccess) {
-        WgradParams wp; memset(&wp, 0, sizeof(wp));
-        wp.B = B; wp.H = H; wp.W = W; wp.tilesX = p.tilesX; wp.tilesY = p.tilesY; wp.n_in = n_in; wp.n_g = 1; wp.nparts = e->nparts;
-        for (int i = 0; i < n_in; ++i) wp.x[i] = b.std_in(in_planes[i], 0);
-        wp.g[0] = b.std_in(g, 0);
-        wp.partial = e->wg_partial; wp.bias_partial = e->wg_bias_partial; wp.zero = e->zero_page; wp.ablate = e->ablate;
-        if (e->math == 4) {   // test hook: reduce the operands' max |x| here (slots at the end of the array, after run_conv's)
-            float* t = e->amax + e->amax_cap - 16;
-            err = hipMemsetAsync(t, 0, 8 * sizeof(float), s);
-            for (int i = 0; i < n_in && err == hipSuccess; ++i) { err = launch_plane_amax(wp.x[i], B, H, W, t + i, s); wp.amax_x[i] = t + i; }
-            if (err == hipSuccess) { err = launch_plane_amax(wp.g[0], B, H, W, t + 5, s); wp.amax_g[0] = t + 5; }
-        }
-        if (err == hipSuccess)
-            err = e->math >= 3 ? launch_wgrad_split(e->math, e->ablate, wp, s) : launch_wgrad_mfma(wp, s);
-        if (err == hipSuccess) {
-            WgradReduceParams rp; memset(&rp, 0, sizeof(rp));
-            rp.partial = e->wg_partial; rp.bias_partial = e->wg_bias_partial; rp.nparts = wp.nparts; rp.n_in = n_in; rp.n_g = 1;
-            rp.cin_total = 32 * n_in; rp.cout_total = 32; rp.shuffle = 0; rp.scale = 1.f; rp.dw = dev_dw_oihw; rp.db = dev_db;
-            err = launch_wgrad_reduce(rp, s);
-        }
-    }
-    hipStreamSynchronize(s);
-    hipFree(fwd); hipFree(bwd);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "bwd launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-// One conv launch with a caller-supplied epilogue per output chunk and, optionally, pixel-shuffled views on either side
-// (include/xsd.h).  Planes and views come from the Builder's own std_in / shuf_in / std_out / shuf_out, the launch goes
-// through run_conv: what is tested is the engine's code.
-int xsd_test_conv3x3_ex(xsd_engine* e, const float* const* in_planes, int n_in, int shuffle_in, const float* dev_w_oihw, const float* dev_bias,
-                        const xsd_test_out* outs, int n_out, int shuffle_out, float* host_amax11, int B, int H, int W, void* stream)
-{
-    if (!e || !in_planes || !outs || !dev_w_oihw || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
-    if (n_in < 1 || n_in > 5 || n_out < 1 || n_out > 5 || (n_in > 1 && n_out > 1)) return fail(XSD_ERR_ARG, "bad n_in/n_out");
-    if ((shuffle_in && n_in != 4) || (shuffle_out && n_out != 4)) return fail(XSD_ERR_ARG, "a pixel-shuffled side has exactly four views");
-    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
-    for (int i = 0; i < (shuffle_in ? 1 : n_in); ++i) if (!in_planes[i]) return fail(XSD_ERR_ARG, "null input plane");
-    for (int j = 0; j < (shuffle_out ? 1 : n_out); ++j) if (!outs[j].p) return fail(XSD_ERR_ARG, "null output plane");
-    hipStream_t s = (hipStream_t)stream;
-    float *fwd = nullptr, *bwd = nullptr;
-    int rc = pack_single(dev_w_oihw, 32 * n_out, 32 * n_in, &fwd, &bwd, e->math, s, e->amax + e->amax_cap - 4);
-    if (rc) return rc;
-    Builder b(e, B, H, W, false, 0);
-    ConvParams p = b.conv_base(0);
-    p.n_in = n_in; p.n_out = n_out; p.wpanel = fwd; p.bias = dev_bias;
-    p.amax_w = e->amax + e->amax_cap - 4;     // mode 4: max |w| of the forward panels (pack_single)
-    for (int i = 0; i < n_in; ++i) p.in[i] = shuffle_in ? b.shuf_in(in_planes[0], 0, i) : b.std_in(in_planes[i], 0);
-    float* oslot = e->amax + e->amax_cap - 24;    // mode 4: one slot per output chunk (CAP-32.. are run_conv's input slots)
-    for (int j = 0; j < n_out; ++j) {
-        const xsd_test_out& t = outs[j];
-        OutDesc& o = p.out[j];
-        if (shuffle_out) b.shuf_out(o, outs[0].p, 0, j); else b.std_out(o, t.p, 0);
-        o.e1 = t.e1; o.e2 = t.e2; o.e3 = t.e3; o.mask = t.mask;
-        o.a1 = t.a1; o.s1 = t.s1; o.a2 = t.a2; o.s2 = t.s2; o.s3 = t.s3; o.slope = t.slope; o.mslope = t.mslope;
-        o.accumulate = t.accumulate; o.bits_out = t.bits_out; o.bits_in = t.bits_in;
-        if (e->math == 4) o.amax = oslot + j;
-    }
-    hipError_t err = e->math == 4 ? hipMemsetAsync(oslot, 0, 5 * sizeof(float), s) : hipSuccess;
-    if (err == hipSuccess) err = run_conv(e, p, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err == hipSuccess && host_amax11) {
-        for (int k = 0; k < 11; ++k) host_amax11[k] = 0.f;
-        if (e->math == 4) {
-            err = hipMemcpy(host_amax11, e->amax + e->amax_cap - 32, n_in * sizeof(float), hipMemcpyDeviceToHost);
-            if (err == hipSuccess) err = hipMemcpy(host_amax11 + 5, p.amax_w, sizeof(float), hipMemcpyDeviceToHost);
-            if (err == hipSuccess) err = hipMemcpy(host_amax11 + 6, oslot, n_out * sizeof(float), hipMemcpyDeviceToHost);
-        }
-    }
-    hipFree(fwd); hipFree(bwd);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "conv launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-// One weight-gradient launch over the n_in x n_g rectangle plus its fixed-order reduction, with the reduction's fields from the caller.
-int xsd_test_wgrad_ex(xsd_engine* e, const float* const* x_planes, int n_in, const float* const* g_planes, int n_g, int shuffle_g,
-                      float scale, int shuffle, int plane, int j0, int n0, int cin_total, int cout_total,
-                      float* dev_dw_oihw, float* dev_db, int B, int H, int W, void* stream)
-{
-    if (!e || !x_planes || !g_planes || !dev_dw_oihw || !dev_db || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
-    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
-    if (n_in < 1 || n_in > 5 || n_g < 1 || n_g > 4) return fail(XSD_ERR_ARG, "bad n_in/n_g (at most 5 X and 4 G planes)");
-    if (shuffle_g && n_g != 4) return fail(XSD_ERR_ARG, "a pixel-shuffled G plane has exactly four views");
-    if (shuffle && n_g != 4) return fail(XSD_ERR_ARG, "the shuffled reduction takes the four sub-pixel gradients (n_g = 4)");
-    const int nparts = wgrad_nparts(e, n_in, n_g);
-    // wg_partial holds nparts x 5 panels, wg_bias_partial nparts x 4 x 32 sums (xsd_create)
-    if ((long long)nparts * n_in * n_g > (long long)e->nparts * 5) return fail(XSD_ERR_ARG, "%d x %d pairs over %d parts do not fit the partial-sum buffer", n_in, n_g, nparts);
-    if (j0 < 0 || n0 < 0 || plane < 0 || cin_total < 32 * (j0 + n_in)) return fail(XSD_ERR_ARG, "the launch's input planes lie outside cin_total");
-    if (shuffle ? cout_total < 128 * (plane + 1) : cout_total < 32 * (n0 + n_g)) return fail(XSD_ERR_ARG, "the launch's output chunks lie outside cout_total");
-    for (int i = 0; i < n_in; ++i) if (!x_planes[i]) return fail(XSD_ERR_ARG, "null X plane");
-    for (int i = 0; i < (shuffle_g ? 1 : n_g); ++i) if (!g_planes[i]) return fail(XSD_ERR_ARG, "null G plane");
-    hipStream_t s = (hipStream_t)stream;
-    Builder b(e, B, H, W, false, 0);
-    WgradParams wp = b.wgrad_base(0);
-    wp.n_in = n_in; wp.n_g = n_g; wp.nparts = nparts;
-    for (int i = 0; i < n_in; ++i) wp.x[i] = b.std_in(x_planes[i], 0);
-    for (int i = 0; i < n_g; ++i) wp.g[i] = shuffle_g ? b.shuf_in(g_planes[0], 0, i) : b.std_in(g_planes[i], 0);
-    wp.partial = e->wg_partial; wp.bias_partial = e->wg_bias_partial; wp.zero = e->zero_page; wp.ablate = e->ablate;
-    hipError_t err = hipSuccess;
-    if (e->math == 4) {   // nobody has reported the operands' max |x|: reduce them here (the weight-gradient hooks' slots, CAP-16 .. CAP-5)
-        float* t = e->amax + e->amax_cap - 16;
-        err = hipMemsetAsync(t, 0, 12 * sizeof(float), s);
-        for (int i = 0; i < n_in && err == hipSuccess; ++i) { err = launch_plane_amax(wp.x[i], B, H, W, t + i, s); wp.amax_x[i] = t + i; }
-        for (int i = 0; i < n_g && err == hipSuccess; ++i) { err = launch_plane_amax(wp.g[i], B, H, W, t + 5 + i, s); wp.amax_g[i] = t + 5 + i; }
-    }
-    if (err == hipSuccess) err = e->math >= 3 ? launch_wgrad_split(e->math, e->ablate, wp, s) : launch_wgrad_mfma(wp, s);
-    if (err == hipSuccess) {
-        WgradReduceParams rp; memset(&rp, 0, sizeof(rp));
-        rp.partial = e->wg_partial; rp.bias_partial = e->wg_bias_partial; rp.nparts = wp.nparts; rp.n_in = n_in; rp.n_g = n_g;
-        rp.cin_total = cin_total; rp.cout_total = cout_total; rp.shuffle = shuffle; rp.scale = scale; rp.j0 = j0; rp.n0 = n0; rp.plane = plane;
-        rp.dw = dev_dw_oihw; rp.db = dev_db;
-        err = launch_wgrad_reduce(rp, s);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-// A dense block's pair-list weight-gradient launch plus the five convs' reductions (include/xsd.h): the launch and the reductions are
-// filled by wgrad_block_fill, the function the plan calls; both partial-sum buffers are all-ones bytes (NaN) when the launch starts.
-int xsd_test_wgrad_block(xsd_engine* e, const float* const* x_planes, const float* const* g_planes, float gscale, float* dev_grads,
-                         const long long* w_off, const long long* b_off, int nparts, int separate_reduces, int* host_nparts,
-                         int B, int H, int W, void* stream)
-{
-    if (!e || !x_planes || !g_planes || !dev_grads || !w_off || !b_off || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null argument or empty shape");
-    if (e->generic) return fail(XSD_ERR_ARG, "single-layer test hooks exist for the 32-filter MFMA path only");
-    if (e->math < 3) return fail(XSD_ERR_ARG, "the pair-list launch belongs to the split math modes (bf16x6, f16x3)");
-    for (int i = 0; i < 5; ++i) if (!x_planes[i] || !g_planes[i]) return fail(XSD_ERR_ARG, "null X or G plane");
-    for (int n = 0; n < 5; ++n) if (w_off[n] < 0 || b_off[n] < 0) return fail(XSD_ERR_ARG, "negative gradient offset");
-    if (nparts == 0) nparts = wgrad_block_nparts(e);
-    const int m = nparts >> 3;
-    if (nparts < 8 || (nparts & 7) > 1 || m > 10) return fail(XSD_ERR_ARG, "nparts = %d: a pair-list launch runs 8 m or 8 m + 1 parts, 1 <= m <= 10", nparts);
-    // wg_partial holds e->nparts x 5 panels, wg_bias_partial e->nparts x 4 x 32 sums (xsd_create)
-    if ((long long)nparts * 15 > (long long)e->nparts * 5 || (long long)nparts * 5 * 32 > (long long)e->nparts * 4 * 32)
-        return fail(XSD_ERR_ARG, "15 panels and 5 x 32 bias sums of %d parts do not fit the partial-sum buffers", nparts);
-    hipStream_t s = (hipStream_t)stream;
-    Builder b(e, B, H, W, false, 0);
-    WgradBlock k;
-    k.wp = b.wgrad_base(0);
-    for (int i = 0; i < 5; ++i) { k.wp.x[i] = b.std_in(x_planes[i], 0); k.wp.g[i] = b.std_in(g_planes[i], 0); }
-    int cin[5], cout[5];
-    for (int n = 0; n < 5; ++n) { cin[n] = 32 * (n + 1); cout[n] = 32; }
-    wgrad_block_fill(k, nparts, cin, cout, gscale, e->wg_partial, e->wg_bias_partial);
-    for (int n = 0; n < 5; ++n) { k.rp[n].dw = dev_grads + w_off[n]; k.rp[n].db = dev_grads + b_off[n]; }
-    k.wp.zero = e->zero_page; k.wp.ablate = e->ablate;
-    hipError_t err = hipSuccess;
-    if (e->math == 4) {   // nobody has reported the operands' max |x|: reduce them here (the weight-gradient hooks' slots, CAP-16 .. CAP-7)
-        float* t = e->amax + e->amax_cap - 16;
-        err = hipMemsetAsync(t, 0, 12 * sizeof(float), s);
-        for (int i = 0; i < 5 && err == hipSuccess; ++i) { err = launch_plane_amax(k.wp.x[i], B, H, W, t + i, s); k.wp.amax_x[i] = t + i; }
-        for (int i = 0; i < 5 && err == hipSuccess; ++i) { err = launch_plane_amax(k.wp.g[i], B, H, W, t + 5 + i, s); k.wp.amax_g[i] = t + 5 + i; }
-    }
-    // a panel or a bias row that no workgroup writes reaches dw / db as NaN, not as the previous launch's value
-    if (err == hipSuccess) err = hipMemsetAsync(e->wg_partial, 0xFF, sizeof(float) * (size_t)e->nparts * 5 * PANEL_FLOATS, s);
-    if (err == hipSuccess) err = hipMemsetAsync(e->wg_bias_partial, 0xFF, sizeof(float) * (size_t)e->nparts * 4 * 32, s);
-    if (err == hipSuccess) err = launch_wgrad_split(e->math, e->ablate, k.wp, s);
-    if (err == hipSuccess) err = wgrad_block_reduce(k, separate_reduces != 0, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "weight-gradient block launch: %s", hipGetErrorString(err));
-    if (host_nparts) *host_nparts = nparts;
-    return XSD_OK;
-}
-
-// ---- the edge layers one by one (include/xsd.h): the engine's packer, the engine's launchers, the engine's block-count rule ----
-// one (32, 9) block through pack_edge_kernel; *packed = the form asked for ([tap][c]), *base = the allocation to free
-static int edge_pack_one(const float* dev_w, int w_last, int flipped, int first_cstride, hipStream_t s, const float** packed, float** base)
-{
-    if (!dev_w) return fail(XSD_ERR_ARG, "null weight block");
-    if (!w_last && first_cstride < 9) return fail(XSD_ERR_ARG, "first_cstride is 9 * in_channels");
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, sizeof(float) * 4 * 288) != hipSuccess) return fail(XSD_ERR_NOMEM, "edge weight forms");
-    hipError_t err = launch_pack_edge(w_last ? nullptr : dev_w, w_last ? dev_w : nullptr, buf, buf + 288, buf + 576, buf + 864, s, w_last ? 9 : first_cstride);
-    if (err != hipSuccess) { hipFree(buf); return fail(XSD_ERR_HIP, "pack_edge launch: %s", hipGetErrorString(err)); }
-    *packed = buf + (w_last ? 576 : 0) + (flipped ? 288 : 0);
-    *base = buf;
-    return XSD_OK;
-}
-static int edge_hook_args(const xsd_engine* e, int B, int H, int W)
-{
-    if (!e || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "null engine or empty shape");
-    if (e->generic) return fail(XSD_ERR_ARG, "the edge kernels belong to the plane path");
-    if (W > EDGE_MAX_W) return fail(XSD_ERR_ARG, "the edge kernels stage rows of at most %d pixels", EDGE_MAX_W);
-    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large");
-    return XSD_OK;
-}
-
-int xsd_test_edge_expand(xsd_engine* e, const float* dev_s, long long s_bs, const float* dev_w, int w_last, int flipped, int first_cstride,
-                         const float* dev_bias, float* dev_out, const float* dev_mask, float mslope, const unsigned short* dev_bits,
-                         int accumulate, float* dev_amax, int B, int H, int W, void* stream)
-{
-    int rc = edge_hook_args(e, B, H, W);
-    if (rc) return rc;
-    if (!dev_s || !dev_out || s_bs < 0) return fail(XSD_ERR_ARG, "null image / output plane or negative stride");
-    hipStream_t s = (hipStream_t)stream;
-    const float* packed = nullptr; float* base = nullptr;
-    if ((rc = edge_pack_one(dev_w, w_last, flipped, first_cstride, s, &packed, &base))) return rc;
-    EdgeExpandParams p; memset(&p, 0, sizeof(p));
-    p.B = B; p.H = H; p.W = W; p.s = dev_s; p.s_bs = s_bs; p.w = packed; p.bias = dev_bias; p.out = dev_out;
-    p.mask = dev_mask; p.mslope = mslope; p.bits = dev_bits; p.accumulate = accumulate; p.amax = dev_amax;
-    hipError_t err = launch_edge_expand(p, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    hipFree(base);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_expand launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_edge_reduce(xsd_engine* e, const float* dev_f, const float* dev_w, int w_last, int flipped, int first_cstride,
-                         const float* dev_bias, const float* dev_skip, long long skip_bs, float* dev_pre, float* dev_y, long long y_bs,
-                         int clamp01, const float* dev_addto, int B, int H, int W, void* stream)
-{
-    int rc = edge_hook_args(e, B, H, W);
-    if (rc) return rc;
-    if (!dev_f || !dev_y || skip_bs < 0 || y_bs < 0) return fail(XSD_ERR_ARG, "null feature plane / output or negative stride");
-    hipStream_t s = (hipStream_t)stream;
-    const float* packed = nullptr; float* base = nullptr;
-    if ((rc = edge_pack_one(dev_w, w_last, flipped, first_cstride, s, &packed, &base))) return rc;
-    EdgeReduceParams p; memset(&p, 0, sizeof(p));
-    p.B = B; p.H = H; p.W = W; p.f = dev_f; p.w = packed; p.bias = dev_bias; p.skip = dev_skip; p.skip_bs = skip_bs;
-    p.pre = dev_pre; p.y = dev_y; p.y_bs = y_bs; p.clamp01 = clamp01; p.addto = dev_addto;
-    hipError_t err = launch_edge_reduce(p, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    hipFree(base);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_reduce launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_edge_wgrad(xsd_engine* e, const float* dev_f, const float* dev_s, long long s_bs, int mode, float* dev_dw, float* dev_db,
-                        int cstride, int nblocks, int* host_nblocks, int B, int H, int W, void* stream)
-{
-    int rc = edge_hook_args(e, B, H, W);
-    if (rc) return rc;
-    if (!dev_f || !dev_s || !dev_dw || !dev_db || s_bs < 0) return fail(XSD_ERR_ARG, "null argument or negative stride");
-    if (mode != 0 && mode != 1) return fail(XSD_ERR_ARG, "mode 0 (conv_first) or 1 (conv_last)");
-    if (cstride < 9) return fail(XSD_ERR_ARG, "cstride is 9 * in_channels");
-    const int rule = edge_wgrad_nblocks();
-    if (nblocks < 0 || nblocks > rule) return fail(XSD_ERR_ARG, "at most %d workgroups (the partial-sum buffer)", rule);
-    hipStream_t s = (hipStream_t)stream;
-    EdgeWgradParams p; memset(&p, 0, sizeof(p));
-    p.B = B; p.H = H; p.W = W; p.f = dev_f; p.s = dev_s; p.s_bs = s_bs; p.partial = e->edge_partial; p.nblocks = nblocks ? nblocks : rule;
-    if (host_nblocks) *host_nblocks = p.nblocks;
-    hipError_t err = launch_edge_wgrad(p, mode, dev_dw, dev_db, s, cstride);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "edge_wgrad launch: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-// ---- the generic-width kernels one by one (include/xsd.h): a GenericNet of one conv, its own pack() / conv() / wgrad() / ew() ----
-static int gconv_hook_args(int cout, int cin, long long param_off, int B, int H, int W)
-{
-    if (cout < 1 || cin < 1 || cout > 4096 || cin > 4096 || param_off < 0 || B < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "bad channel counts, offset or shape");
-    if ((long long)H * W > (1ll << 24) || (long long)B * H * W > (1ll << 26)) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
-    return XSD_OK;
-}
-
-int xsd_test_gconv(int cout, int cin, const float* dev_params, long long param_off, int transposed, const xsd_test_gconv_args* a,
-                   int B, int H, int W, int* host_path, void* stream)
-{
-    int rc = gconv_hook_args(cout, cin, param_off, B, H, W);
-    if (rc) return rc;
-    if (!dev_params || !a || !a->x || !a->y) return fail(XSD_ERR_ARG, "null argument");
-    if (a->shuffle && ((transposed ? cin : cout) & 3)) return fail(XSD_ERR_ARG, "a pixel-shuffled output has a multiple of four channels");
-    if (a->e1 && (a->e1c < 0 || a->e1c > (transposed ? cin : cout))) return fail(XSD_ERR_ARG, "e1c lies outside the output channels");
-    if (a->skip && a->skipc != 1 && a->skipc != (transposed ? cin : cout)) return fail(XSD_ERR_ARG, "skipc is 1 or the output channel count");
-    hipStream_t s = (hipStream_t)stream;
-    GenericNet* n = GenericNet::create_convs(1, &cout, &cin, param_off);
-    if (!n) return fail(XSD_ERR_NOMEM, "generic-width conv: device allocation failed");
-    hipError_t err = n->pack(dev_params, s);
-    if (err == hipSuccess) err = n->test_conv(s, 0, transposed != 0, *a, B, H, W);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (host_path) *host_path = n->last_path;
-    delete n;
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width conv: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_gwgrad(int cout, int cin, long long param_off, const float* dev_x, long long xbs, const float* dev_g, long long gbs,
-                    float* dev_grads, int B, int H, int W, int* host_path, int* host_parts, void* stream)
-{
-    int rc = gconv_hook_args(cout, cin, param_off, B, H, W);
-    if (rc) return rc;
-    if (!dev_x || !dev_g || !dev_grads) return fail(XSD_ERR_ARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    GenericNet* n = GenericNet::create_convs(1, &cout, &cin, param_off);
-    if (!n) return fail(XSD_ERR_NOMEM, "generic-width weight gradient: device allocation failed");
-    hipError_t err = n->test_wgrad(s, 0, dev_x, xbs, dev_g, gbs, B, H, W, dev_grads);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (host_path) *host_path = n->last_path;
-    if (host_parts) *host_parts = n->last_parts;
-    delete n;
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width weight gradient: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_gop(int op, float* dev_d, long long dbs, const float* dev_s, long long sbs, const float* dev_s2, int B, int C, int H, int W,
-                 float a, void* stream)
-{
-    if (op < 0 || op > 5 || !dev_d || !dev_s || B < 1 || C < 1 || H < 1 || W < 1) return fail(XSD_ERR_ARG, "bad op, null argument or empty shape");
-    if ((op == 3 || op == 5) && !dev_s2) return fail(XSD_ERR_ARG, "op %d reads a second tensor", op);
-    if (op == 3 && (C & 3)) return fail(XSD_ERR_ARG, "the unshuffle writes a multiple of four channels");
-    if ((long long)B * C * H * W > (1ll << 28)) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
-    hipStream_t s = (hipStream_t)stream;
-    const int one = 1;
-    GenericNet* n = GenericNet::create_convs(1, &one, &one, 0);
-    if (!n) return fail(XSD_ERR_NOMEM, "generic-width op: device allocation failed");
-    hipError_t err = n->test_op(s, op, dev_d, dbs, dev_s, sbs, dev_s2, B, C, H, W, a);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    delete n;
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width op %d: %s", op, hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_gpack(int nconv, const int* host_cout, const int* host_cin, const float* dev_params, float* dev_wt, long long wt_cap,
-                   float* dev_wblk, long long wblk_cap, long long* host_off, long long* host_count, void* stream)
-{
-    if (nconv < 1 || nconv > 8 || !host_cout || !host_cin || !dev_params || !host_off || !host_count) return fail(XSD_ERR_ARG, "bad table or null argument");
-    for (int i = 0; i < nconv; ++i)
-        if (host_cout[i] < 1 || host_cin[i] < 1 || host_cout[i] > 4096 || host_cin[i] > 4096) return fail(XSD_ERR_ARG, "bad channel counts");
-    hipStream_t s = (hipStream_t)stream;
-    GenericNet* n = GenericNet::create_convs(nconv, host_cout, host_cin, 0);
-    if (!n) return fail(XSD_ERR_NOMEM, "generic-width pack: device allocation failed");
-    for (int i = 0; i < nconv; ++i) { host_off[3 * i] = n->convs[i].t; host_off[3 * i + 1] = n->convs[i].pf; host_off[3 * i + 2] = n->convs[i].pt; }
-    host_count[0] = n->wt_floats; host_count[1] = n->wblk_floats;
-    if ((dev_wt && wt_cap < n->wt_floats) || (dev_wblk && wblk_cap < n->wblk_floats)) { delete n; return fail(XSD_ERR_ARG, "a read-back buffer is too small"); }
-    hipError_t err = n->pack(dev_params, s);
-    if (err == hipSuccess && dev_wt) err = hipMemcpyAsync(dev_wt, n->wt, sizeof(float) * n->wt_floats, hipMemcpyDeviceToDevice, s);
-    if (err == hipSuccess && dev_wblk && n->wblk_floats) err = hipMemcpyAsync(dev_wblk, n->wblk, sizeof(float) * n->wblk_floats, hipMemcpyDeviceToDevice, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    delete n;
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "generic-width pack: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-// ---- the loss kernels scale by scale, the pooling and the plane path's clamp backward (include/xsd.h) ----
-int xsd_loss_test_scale(const xsd_loss_config* cfg, const float* dev_y, const float* dev_target, const float* dev_gup, const float* dev_coarse,
-                        float* dev_dy, int accumulate, double* dev_stat, float* host_scal11, int B, int H, int W, void* stream)
-{
-    if (!cfg || !dev_y || !dev_target || !dev_stat || !host_scal11) return fail(XSD_ERR_ARG, "null argument");
-    if (!(cfg->sigma > 0.f)) return fail(XSD_ERR_ARG, "loss: sigma must be > 0");
-    if ((dev_dy != nullptr) != (dev_gup != nullptr)) return fail(XSD_ERR_ARG, "dy and the upstream pair come together");
-    if (dev_coarse && !dev_dy) return fail(XSD_ERR_ARG, "a coarse gradient needs dy");
-    LossWeights w;
-    for (int i = 0; i < 5; ++i) w.w[i] = 0.f;
-    w.w[3] = 1.f;                                  // what loss_check refuses for ssim
-    w.correction = 0.f; w.sigma = cfg->sigma; w.k1 = cfg->k1; w.k2 = cfg->k2; w.kernel_size = cfg->kernel_size;
-    const char* why = nullptr;
-    if (loss_check(w, B, H, W, &why)) return fail(XSD_ERR_ARG, why);
-    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
-    hipError_t err = loss_test_scale(w, dev_y, dev_target, dev_gup, dev_coarse, dev_dy, accumulate, dev_stat, host_scal11, B, H, W, (hipStream_t)stream);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "loss scale: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_loss_test_pool2(const float* dev_p, const float* dev_t, float* dev_po, float* dev_to, int B, int H, int W, void* stream)
-{
-    if (!dev_p || !dev_t || !dev_po || !dev_to || B < 1 || H < 2 || W < 2) return fail(XSD_ERR_ARG, "null argument or an image under 2 x 2");
-    if ((long long)B * H > 0x7fffffffll / W) return fail(XSD_ERR_ARG, "shape too large for a kernel test");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t err = loss_test_pool2(dev_p, dev_t, dev_po, dev_to, B, H, W, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "pool2: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_clamp_bwd(const float* dev_pre, const float* dev_dy, float* dev_dpre, int64_t n, void* stream)
-{
-    if (!dev_pre || !dev_dy || !dev_dpre || n <= 0) return fail(XSD_ERR_ARG, "null argument or n <= 0");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t err = launch_clamp_bwd(dev_pre, dev_dy, dev_dpre, n, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "clamp backward: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_packed_region(xsd_engine* e, int region, void* dev_dst, int64_t dst_bytes, int64_t* info, void* stream)
-{
-    if (!e || !info) return fail(XSD_ERR_ARG, "null argument");
-    if (e->generic) return fail(XSD_ERR_ARG, "xsd_test_packed_region: a generic-width engine has no plane panels");
-    if (region < 0 || region >= XSD_PACKED_REGIONS) return fail(XSD_ERR_ARG, "xsd_test_packed_region: unknown region %d", region);
-    if (!e->packed) return fail(XSD_ERR_STATE, "xsd_test_packed_region needs a preceding xsd_pack_weights");
-    const int ci = e->cfg.in_channels, co = e->cfg.out_channels, nup = (int)e->up.size();
-    const void* src = nullptr;
-    int64_t bytes = 0;
-    std::vector<int64_t> table;
-    switch (region) {
-    case XSD_PACKED_PK_FWD: src = e->pk_fwd; bytes = 4 * e->pk_floats; break;
-    case XSD_PACKED_PK_BWD: src = e->pk_bwd; bytes = 4 * e->pk_floats; break;
-    case XSD_PACKED_PK_FWD_S: src = e->pk_fwd_s; bytes = 4 * e->pk_floats; break;
-    case XSD_PACKED_PK_BWD_S: src = e->pk_bwd_s; bytes = 4 * e->pk_floats; break;
-    case XSD_PACKED_AMAX: src = e->amax; bytes = 2 * 4; break;
-    case XSD_PACKED_PK_EDGE: src = e->pk_edge; bytes = 4ll * 2 * 288 * e->planes * (ci + co); break;
-    case XSD_PACKED_PK_SBIAS: src = e->pk_sbias; for (auto& c : e->up) bytes += 4ll * c.cout; break;
-    case XSD_PACKED_PARAMS_PAD: src = e->params_pad; bytes = e->nf_pad ? 4 * e->nparams_pad : 0; break;
-    default: {  // XSD_PACKED_TABLE: the descriptors the pack kernels read, copied back from the device
-        std::vector<PackDesc> descs(e->ndesc);
-        HIPCHK(hipMemcpy(descs.data(), e->descs_dev, sizeof(PackDesc) * descs.size(), hipMemcpyDeviceToHost));
-        table = {e->ndesc, nup, e->first_w, e->last_w, e->planes, e->nf_pad, e->pk_floats, e->nf_pad ? e->nparams_pad : e->nparams};
-        for (auto& d : descs) {
-            unsigned int bits; memcpy(&bits, &d.bwd_scale, 4);
-            table.insert(table.end(), {d.src_w, d.dst_fwd, d.dst_bwd, d.cout, d.cin, d.shuffle, (int64_t)bits});
-        }
-        for (auto& c : e->up) table.insert(table.end(), {c.b_off, c.sbias_off});
-        bytes = 8 * (int64_t)table.size();
-    } }
-    info[0] = bytes;
-    if (!dev_dst) return XSD_OK;
-    if (dst_bytes < bytes) return fail(XSD_ERR_ARG, "xsd_test_packed_region: region %d holds %lld bytes, the buffer %lld", region, (long long)bytes, (long long)dst_bytes);
-    if (bytes == 0) return XSD_OK;
-    if (region == XSD_PACKED_TABLE) { memcpy(dev_dst, table.data(), (size_t)bytes); return XSD_OK; }
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t err = hipMemcpyAsync(dev_dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "packed region %d: %s", region, hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_pad_gather(xsd_engine* e, float* dev_grads_real, const float* dev_grads_padded, void* stream)
-{
-    if (!e || !dev_grads_real || !dev_grads_padded) return fail(XSD_ERR_ARG, "null argument");
-    if (e->generic || !e->nf_pad) return fail(XSD_ERR_ARG, "xsd_test_pad_gather: the engine's width is not zero-padded");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(pad_params_kernel, dim3(64, e->npad), dim3(256), 0, s, dev_grads_real, const_cast<float*>(dev_grads_padded), static_cast<const PadDesc*>(e->pad_descs), 1);
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "pad gather: %s", hipGetErrorString(err));
-    return XSD_OK;
-}
-
-int xsd_test_add_channels(float* dev_dst, const float* dev_src, int C, int64_t HW, int B, void* stream)
-{
-    if (!dev_dst || !dev_src || C < 1 || HW < 1 || B < 1) return fail(XSD_ERR_ARG, "null argument or an extent < 1");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t err = launch_add_channels(dev_dst, dev_src, C, HW, B, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
-    if (err != hipSuccess) return fail(XSD_ERR_HIP, "add channels: %s", hipGetErrorString(err));
     return XSD_OK;
 }
 
