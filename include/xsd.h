@@ -43,7 +43,10 @@ enum xsd_status {
     XSD_ERR_ARG = -1,     /* bad argument / unsupported configuration */
     XSD_ERR_HIP = -2,     /* a HIP runtime call failed */
     XSD_ERR_STATE = -3,   /* call sequence error (e.g. backward without a saved forward) */
-    XSD_ERR_NOMEM = -4
+    XSD_ERR_NOMEM = -4    /* a device (or host) allocation failed -- in every create, every growth path and xsd_debug_stamps, whatever the family.  What the
+                             call had allocated before is freed again; a create leaves *out as it was; a handle that could not grow
+                             keeps no half-built state: its held shape and the refused one both work at the next call, with the
+                             results of a fresh handle, and its destroy gives everything back (tests/test_hip_lifetime.py) */
 };
 
 enum xsd_kind { XSD_KIND_DN = 0, XSD_KIND_SR = 1 };
@@ -839,6 +842,17 @@ int xsd_test_packed_region(xsd_engine* e, int region, void* dev_dst, int64_t dst
 int xsd_test_pad_gather(xsd_engine* e, float* dev_grads_real, const float* dev_grads_padded, void* stream);
 /* launch_add_channels alone (csrc/aux_kernels.hip): dst[B][HW] += sum over the C channels of src[B][C][HW]. */
 int xsd_test_add_channels(float* dev_dst, const float* dev_src, int C, int64_t HW, int B, void* stream);
+
+/* The device-memory ledger (csrc/xsd_ledger.h, csrc/xsd_mem.h): every device allocation of the library and every free goes through one
+ * account, per loaded library and process-wide (all handles, all threads).  Host code only, on no product path, no device call.
+ * xsd_test_mem_stats: copies the first n (1..6) counters into out (host): live_blocks, live_bytes (allocations held now and their
+ *   bytes as asked for), allocs, frees (since the library was loaded), foreign_frees (a free of a non-null pointer the ledger never
+ *   handed out), refused (allocations refused by the arm below).  XSD_ERR_ARG for null out or n outside 1..6.
+ * xsd_test_mem_refuse: nth >= 1 arms a one-shot refusal: the nth device allocation from now fails as out of memory WITHOUT calling the
+ *   runtime (the entry that asked answers XSD_ERR_NOMEM); the arm is spent when it fires.  nth = 0 disarms.  Returns the number of
+ *   allocation attempts since the previous call of this entry: arm-free runs measure how many allocations a path makes. */
+int xsd_test_mem_stats(int64_t* out, int n);
+int64_t xsd_test_mem_refuse(int64_t nth);
 
 #ifdef __cplusplus
 }

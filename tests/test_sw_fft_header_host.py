@@ -24,7 +24,7 @@ def test_one_copy_of_the_passes_in_the_header():
     assert '#include "sw_fft.h"' in fused and "fft_twiddles(H, W, t.data())" in fused
     assert "#ifndef XSD_SW_FFT_H" in hdr and re.search(r"^namespace \{", hdr, re.M)
     # a kernel that allocates, waits or uses atomics would not fit an asynchronous caller
-    assert "hipMalloc" not in hdr and "Synchronize" not in hdr and not re.search(r"atomic\w*\s*\(", hdr)
+    assert "hipMalloc" not in hdr and "dev_alloc" not in hdr and "Synchronize" not in hdr and not re.search(r"atomic\w*\s*\(", hdr)
 
 
 def test_the_makefile_rebuilds_on_a_change_of_the_header():

@@ -28,6 +28,7 @@
 #include "../../include/xsd.h"
 
 #include "xsd_err.h"
+#include "xsd_mem.h"
 #define fail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
@@ -611,7 +612,7 @@ int xsd_ext_metrics_create(xsd_ext_metrics** out)
 void xsd_ext_metrics_destroy(xsd_ext_metrics* m)
 {
     if (!m) return;
-    hipFree(m->ws);
+    xsd::dev_free(m->ws);
     delete m;
 }
 
@@ -639,9 +640,9 @@ int xsd_ext_metrics_eval(xsd_ext_metrics* m, const float* dev_preds, const float
     const size_t o_haar = L.o_haar, o_md1 = L.o_md1, o_md2 = L.o_md2, o_ux = L.o_ux, o_uy = L.o_uy, o_mx = L.o_mx, o_my = L.o_my;
     if (L.bytes > m->ws_bytes) {
         EXTM_HIPCHK(hipStreamSynchronize(st));
-        if (m->ws) EXTM_HIPCHK(hipFree(m->ws));
+        if (m->ws) EXTM_HIPCHK(xsd::dev_free(m->ws));
         m->ws = nullptr; m->ws_bytes = 0; m->B = 0;
-        if (hipMalloc(&m->ws, L.bytes) != hipSuccess)
+        if (xsd::dev_alloc(&m->ws, L.bytes) != hipSuccess)
             return fail(XSD_ERR_NOMEM, "xsd_ext_metrics_eval: workspace allocation of %zu bytes failed", L.bytes);
         m->ws_bytes = L.bytes;
     }

@@ -32,6 +32,7 @@
 #include "../../include/xsd.h"
 
 #include "xsd_err.h"
+#include "xsd_mem.h"
 #define fail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
@@ -350,9 +351,9 @@ struct Plan {
 
 void free_plan(Plan& p)
 {
-    if (p.Ww && p.Ww != p.Wh) hipFree(p.Ww);
-    if (p.Wh) hipFree(p.Wh);
-    if (p.filt) hipFree(p.filt);
+    if (p.Ww && p.Ww != p.Wh) xsd::dev_free(p.Ww);
+    if (p.Wh) xsd::dev_free(p.Wh);
+    if (p.filt) xsd::dev_free(p.filt);
     p = Plan();
 }
 
@@ -451,7 +452,7 @@ namespace {
 
 int upload(void** dst, const void* src, size_t bytes)
 {
-    if (hipMalloc(dst, bytes) != hipSuccess) { *dst = nullptr; return fail(XSD_ERR_NOMEM, "xsd_fsim: plan allocation of %zu bytes failed", bytes); }
+    if (xsd::dev_alloc(dst, bytes) != hipSuccess) { *dst = nullptr; return fail(XSD_ERR_NOMEM, "xsd_fsim: plan allocation of %zu bytes failed", bytes); }
     FSIM_HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
     FSIM_HIPCHK(hipDeviceSynchronize());      // stream 0's upload is on the device before the eval's launches on a non-blocking stream read the plan
     return XSD_OK;
@@ -491,9 +492,9 @@ int reserve(xsd_fsim* m, size_t bytes, hipStream_t st, const char* who)
 {
     if (bytes <= m->ws_bytes) return XSD_OK;
     FSIM_HIPCHK(hipStreamSynchronize(st));
-    if (m->ws) FSIM_HIPCHK(hipFree(m->ws));
+    if (m->ws) FSIM_HIPCHK(xsd::dev_free(m->ws));
     m->ws = nullptr; m->ws_bytes = 0;
-    if (hipMalloc(&m->ws, bytes) != hipSuccess) return fail(XSD_ERR_NOMEM, "%s: workspace allocation of %zu bytes failed", who, bytes);
+    if (xsd::dev_alloc(&m->ws, bytes) != hipSuccess) return fail(XSD_ERR_NOMEM, "%s: workspace allocation of %zu bytes failed", who, bytes);
     m->ws_bytes = bytes;
     return XSD_OK;
 }
@@ -554,7 +555,7 @@ void xsd_fsim_destroy(xsd_fsim* m)
 {
     if (!m) return;
     for (Plan& p : m->plans) free_plan(p);
-    hipFree(m->ws);
+    xsd::dev_free(m->ws);
     delete m;
 }
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "generic_net.h"
+#include "xsd_mem.h"
 
 namespace xsd {
 
@@ -506,7 +507,7 @@ static inline int ew_grid(long long n) { long long g = (n + 255) / 256; return (
 
 GenericNet::~GenericNet()
 {
-    hipFree(wt); hipFree(wblk); hipFree(descs_dev); hipFree(ws); hipFree(wg_partial); hipFree(wg_bias_partial);
+    xsd::dev_free(wt); xsd::dev_free(wblk); xsd::dev_free(descs_dev); xsd::dev_free(ws); xsd::dev_free(wg_partial); xsd::dev_free(wg_bias_partial);
 }
 
 // The conv table of a net: flat-parameter, transposed-copy and block-packed offsets in creation order, one pack descriptor per conv
@@ -535,12 +536,12 @@ static bool gtable_alloc(GenericNet* n, const GTable& t)
     for (auto& q : t.d) maxw = std::max(maxw, q.cout * q.cin * 9);
     n->max_w = maxw;
     n->wblk_floats = t.boff;
-    return hipMalloc((void**)&n->wt, sizeof(float) * t.toff) == hipSuccess &&
-           (!t.boff || hipMalloc((void**)&n->wblk, sizeof(float) * t.boff) == hipSuccess) &&
-           hipMalloc((void**)&n->descs_dev, sizeof(GPackDesc) * t.d.size()) == hipSuccess &&
+    return xsd::dev_alloc((void**)&n->wt, sizeof(float) * t.toff) == hipSuccess &&
+           (!t.boff || xsd::dev_alloc((void**)&n->wblk, sizeof(float) * t.boff) == hipSuccess) &&
+           xsd::dev_alloc((void**)&n->descs_dev, sizeof(GPackDesc) * t.d.size()) == hipSuccess &&
            hipMemcpy(n->descs_dev, t.d.data(), sizeof(GPackDesc) * t.d.size(), hipMemcpyHostToDevice) == hipSuccess &&
-           hipMalloc((void**)&n->wg_partial, sizeof(float) * (size_t)GenericNet::MAX_PARTS * maxw) == hipSuccess &&
-           hipMalloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) == hipSuccess &&   // parts * cout <= capacity / (9 cin)
+           xsd::dev_alloc((void**)&n->wg_partial, sizeof(float) * (size_t)GenericNet::MAX_PARTS * maxw) == hipSuccess &&
+           xsd::dev_alloc((void**)&n->wg_bias_partial, sizeof(float) * ((size_t)GenericNet::MAX_PARTS * maxw / 9 + 1)) == hipSuccess &&   // parts * cout <= capacity / (9 cin)
            hipDeviceSynchronize() == hipSuccess;      // the descriptors (stream 0) are on the device before a pack on a non-blocking stream reads them
 }
 
@@ -634,8 +635,8 @@ hipError_t GenericNet::plan(int B_, int H_, int W_, bool train_)
         }
         if (!pass) {
             if (a.top > ws_bytes) {
-                if (ws) { hipDeviceSynchronize(); hipFree(ws); ws = nullptr; ws_bytes = 0; }
-                GCHK(hipMalloc((void**)&ws, a.top));
+                if (ws) { hipDeviceSynchronize(); xsd::dev_free(ws); ws = nullptr; ws_bytes = 0; }
+                GCHK(xsd::dev_alloc((void**)&ws, a.top));
                 ws_bytes = a.top;
             }
         }

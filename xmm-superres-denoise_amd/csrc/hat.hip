@@ -387,7 +387,6 @@ extern "C" {
 int xsd_hat_create(const xsd_hat_config* cfg, xsd_hat** out)
 {
     if (!cfg || !out) return rfail(XSD_ERR_ARG, "null argument");
-    *out = nullptr;
     const auto& c = *cfg;
     if (c.ape) return rfail(XSD_ERR_ARG, "HAT: ape=True (absolute position embedding) is not supported by the MI355X engine");
     if (c.upsampler != 0)
@@ -561,14 +560,14 @@ int xsd_hat_test_channel_mean(const float* dev_x, float* dev_mean, int B, int64_
     hipStream_t s = (hipStream_t)stream;
     const int nchunk = pool_chunks(HW);
     double* part = nullptr;
-    if (hipMalloc((void**)&part, sizeof(double) * (size_t)B * nchunk * C) != hipSuccess) {
+    if (xsd::dev_alloc((void**)&part, sizeof(double) * (size_t)B * nchunk * C) != hipSuccess) {
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "HAT pool test: allocation failed");
     }
     hipError_t e = pool_partial(s, dev_x, part, B, HW, C);
     if (!e) e = ca(s, part, B, HW, C, 0, nullptr, nullptr, nullptr, nullptr, dev_mean, nullptr);
     hipStreamSynchronize(s);
-    hipFree(part);
+    xsd::dev_free(part);
     if (e) return rfail(XSD_ERR_HIP, "HAT pool test: %s", hipGetErrorString(e));
     return XSD_OK;
 }
@@ -594,10 +593,10 @@ int xsd_hat_test_ca_combine(float* dev_x, const float* dev_t, const float* dev_w
     if (Cs < 1 || Cs > 4096) return rfail(XSD_ERR_ARG, "HAT combine test: a squeezed width of %d is outside [1, 4096]", Cs);
     double* part = nullptr;
     float* gates = nullptr;
-    if (hipMalloc((void**)&part, sizeof(double) * (size_t)B * pool_chunks(HW) * C) != hipSuccess ||
-        hipMalloc((void**)&gates, sizeof(float) * (size_t)B * C) != hipSuccess) {
+    if (xsd::dev_alloc((void**)&part, sizeof(double) * (size_t)B * pool_chunks(HW) * C) != hipSuccess ||
+        xsd::dev_alloc((void**)&gates, sizeof(float) * (size_t)B * C) != hipSuccess) {
         (void)hipGetLastError();
-        if (part) hipFree(part);
+        if (part) xsd::dev_free(part);
         return rfail(XSD_ERR_NOMEM, "HAT combine test: allocation failed");
     }
     hipError_t e = pool_partial(s, dev_t, part, B, HW, C);
@@ -605,8 +604,8 @@ int xsd_hat_test_ca_combine(float* dev_x, const float* dev_t, const float* dev_w
     if (!e) e = combine(s, dev_x, dev_t, gates, scale, B, HW, C);
     if (!e && dev_y) e = hipMemcpyAsync(dev_y, gates, sizeof(float) * (size_t)B * C, hipMemcpyDeviceToDevice, s);
     hipStreamSynchronize(s);
-    hipFree(part);
-    hipFree(gates);
+    xsd::dev_free(part);
+    xsd::dev_free(gates);
     if (e) return rfail(XSD_ERR_HIP, "HAT combine test: %s", hipGetErrorString(e));
     return XSD_OK;
 }

@@ -13,6 +13,7 @@
 // the kernels are plain LDS-tiled separable filters with deterministic two-stage reductions (no atomics, no host
 // synchronisation: every scalar the next kernel needs stays on the device).
 #include "xsd_loss.h"
+#include "xsd_mem.h"
 
 namespace xsd {
 
@@ -619,7 +620,7 @@ hipError_t loss_test_scale(const LossWeights& w, const float* y, const float* t,
     size_t total = 0;
     for (size_t b : sizes) total += (b + 255) & ~(size_t)255;
     char* ws = nullptr;
-    hipError_t err = hipMalloc((void**)&ws, total);
+    hipError_t err = xsd::dev_alloc((void**)&ws, total);
     if (err != hipSuccess) return err;
     size_t off = 0;
     auto carve = [&](size_t bytes) { char* p = ws + off; off += (bytes + 255) & ~(size_t)255; return p; };
@@ -633,7 +634,7 @@ hipError_t loss_test_scale(const LossWeights& w, const float* y, const float* t,
     if (err == hipSuccess) err = hipStreamSynchronize(s); else hipStreamSynchronize(s);
     ScaleScal h;
     if (err == hipSuccess) err = hipMemcpy(&h, r.sc, sizeof(h), hipMemcpyDeviceToHost);
-    hipFree(ws);
+    xsd::dev_free(ws);
     if (err != hipSuccess) return err;
     const float out[11] = {h.pmin, h.pmax, h.tmin, h.tmax, h.dr, h.c1, h.c2, (float)h.from_p, h.nmax, h.nmin, h.ddr};
     for (int i = 0; i < 11; ++i) scal11[i] = out[i];

@@ -20,6 +20,8 @@
 
 #include <algorithm>
 
+#include "xsd_mem.h"
+
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -169,8 +171,8 @@ hipError_t run_probe(double seconds, double* tflops, double* ghz, hipStream_t st
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t rc = hipSuccess;
     auto fail = [&](const char*, hipError_t err) { rc = err; };
-    if ((e = hipMalloc(&d_src, L::BYTES)) != hipSuccess || (e = hipMalloc(&d_out, sizeof(float) * 512 * G)) != hipSuccess ||
-        (e = hipMalloc(&d_clk, sizeof(unsigned long long) * 2 * G)) != hipSuccess) fail("hipMalloc", e);
+    if ((e = xsd::dev_alloc(&d_src, L::BYTES)) != hipSuccess || (e = xsd::dev_alloc(&d_out, sizeof(float) * 512 * G)) != hipSuccess ||
+        (e = xsd::dev_alloc(&d_clk, sizeof(unsigned long long) * 2 * G)) != hipSuccess) fail("dev_alloc", e);
     if (rc == hipSuccess && (e = hipMemcpyAsync(d_src, img.data(), L::BYTES, hipMemcpyHostToDevice, st)) != hipSuccess) fail("hipMemcpy", e);
     if (rc == hipSuccess && (e = hipStreamSynchronize(st)) != hipSuccess) fail("sync", e);
     if (rc == hipSuccess && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mfma_stream_kernel<BF>), hipFuncAttributeMaxDynamicSharedMemorySize, L::BYTES)) != hipSuccess) fail("LDS size", e);
@@ -213,7 +215,7 @@ hipError_t run_probe(double seconds, double* tflops, double* ghz, hipStream_t st
     }
     if (e0) hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
-    hipFree(d_src); hipFree(d_out); hipFree(d_clk);
+    xsd::dev_free(d_src); xsd::dev_free(d_out); xsd::dev_free(d_clk);
     return rc;
 }
 

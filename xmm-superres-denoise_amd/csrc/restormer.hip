@@ -38,6 +38,7 @@
 #include "../../include/xsd.h"
 
 #include "xsd_err.h"
+#include "xsd_mem.h"
 #define rfail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
@@ -563,8 +564,8 @@ struct xsd_restormer {
 
     ~xsd_restormer()
     {
-        if (wt) hipFree(wt);
-        if (ws) hipFree(ws);
+        if (wt) xsd::dev_free(wt);
+        if (ws) xsd::dev_free(ws);
     }
 };
 
@@ -754,7 +755,6 @@ extern "C" {
 int xsd_restormer_create(const xsd_restormer_config* cfg, xsd_restormer** out)
 {
     if (!cfg || !out) return rfail(XSD_ERR_ARG, "null argument");
-    *out = nullptr;
     const auto& c = *cfg;
     if (c.dual_pixel_task) return rfail(XSD_ERR_ARG, "Restormer: dual_pixel_task is not supported by the MI355X engine");
     if (c.inp_channels < 1 || c.inp_channels > 1024 || c.out_channels != c.inp_channels)
@@ -778,7 +778,7 @@ int xsd_restormer_create(const xsd_restormer_config* cfg, xsd_restormer** out)
     r->cfg = c;
     r->dim = c.dim;
     layout(r);
-    if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess) {
+    if (xsd::dev_alloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess) {
         (void)hipGetLastError();
         delete r;
         return rfail(XSD_ERR_NOMEM, "Restormer: packed-weight allocation failed");
@@ -824,11 +824,11 @@ int xsd_restormer_forward(xsd_restormer* r, const float* dev_x, float* dev_y, in
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + r->ws_bytes)
                 return rfail(XSD_ERR_NOMEM, "Restormer: a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held "
                              "by this engine of %.1f GiB); use a smaller batch per call", need * gb, B, H, W, free_b * gb, r->ws_bytes * gb, total_b * gb);
-            if (r->ws) { hipDeviceSynchronize(); hipFree(r->ws); r->ws = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
-            hipError_t err = hipMalloc((void**)&r->ws, need);
+            if (r->ws) { hipDeviceSynchronize(); xsd::dev_free(r->ws); r->ws = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
+            hipError_t err = xsd::dev_alloc((void**)&r->ws, need);
             if (err != hipSuccess) {
                 (void)hipGetLastError();
-                return rfail(XSD_ERR_NOMEM, "Restormer: workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s", need * gb, B, H, W, hipGetErrorString(err));
+                return rfail(XSD_ERR_NOMEM, "Restormer: workspace allocation (%.1f GiB for %d x %d x %d tiles) failed: %s", need * gb, B, H, W, hipGetErrorString(err));
             }
             r->ws_bytes = need;
         }
@@ -881,11 +881,11 @@ int check_grid(const char* what, int B, long long HW)
 
 struct Scratch {                       // device allocations of one hook call
     std::vector<void*> ptrs;
-    ~Scratch() { for (void* p : ptrs) hipFree(p); }
+    ~Scratch() { for (void* p : ptrs) xsd::dev_free(p); }
     void* get(size_t bytes)
     {
         void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (xsd::dev_alloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         ptrs.push_back(p);
         return p;
     }

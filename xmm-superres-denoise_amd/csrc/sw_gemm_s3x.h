@@ -300,7 +300,7 @@ int ready_math(SwBase* r, const char* net, hipStream_t s)
     if (!r->wt3) {
         long long n = 0;
         for (Lin* p : r->lins) p->t3 = add(n, 3 * sx_plane_elems(p->cout, p->cin * p->taps));
-        if (hipMalloc((void**)&r->wt3, sizeof(unsigned short) * std::max(8ll, n)) != hipSuccess) {
+        if (xsd::dev_alloc((void**)&r->wt3, sizeof(unsigned short) * std::max(8ll, n)) != hipSuccess) {
             (void)hipGetLastError();
             r->wt3 = nullptr;
             return rfail(XSD_ERR_NOMEM, "%s: allocation of the bf16x6 weight planes failed", net);
@@ -334,7 +334,7 @@ int test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, flo
     const long long wn = (long long)N * K;
     const size_t bytes = math == 3 ? sizeof(unsigned short) * (size_t)(3 * sx_plane_elems(N, K)) : sizeof(float) * (size_t)wn;
     void* wp = nullptr;
-    if (hipMalloc(&wp, bytes) != hipSuccess) {
+    if (xsd::dev_alloc(&wp, bytes) != hipSuccess) {
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "GEMM test: allocation failed");
     }
@@ -354,7 +354,7 @@ int test_gemm(const float* dev_a, const float* dev_w, const float* dev_bias, flo
         e = math == 3 ? gemm_s3x(s, p, (const unsigned short*)wp) : gemm(s, p);
     }
     hipStreamSynchronize(s);
-    hipFree(wp);
+    xsd::dev_free(wp);
     if (e) return rfail(XSD_ERR_HIP, "GEMM test: %s", hipGetErrorString(e));
     return XSD_OK;
 }
@@ -419,7 +419,7 @@ int test_gemm_view(const xsd_sw_gemm_view* v, hipStream_t s)
     const long long wn = (long long)N * K;
     const size_t bytes = v->math == 3 ? sizeof(unsigned short) * (size_t)(3 * sx_plane_elems(N, K)) : sizeof(float) * (size_t)wn;
     void* wp = nullptr;
-    if (hipMalloc(&wp, bytes) != hipSuccess) {
+    if (xsd::dev_alloc(&wp, bytes) != hipSuccess) {
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "GEMM view test: allocation failed");
     }
@@ -451,7 +451,7 @@ int test_gemm_view(const xsd_sw_gemm_view* v, hipStream_t s)
         e = v->math == 3 ? gemm_s3x(s, p, (const unsigned short*)wp) : gemm(s, p);
     }
     hipStreamSynchronize(s);
-    hipFree(wp);
+    xsd::dev_free(wp);
     if (e) return rfail(XSD_ERR_HIP, "GEMM view test: %s", hipGetErrorString(e));
     return XSD_OK;
 }

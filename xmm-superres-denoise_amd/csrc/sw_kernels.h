@@ -34,6 +34,7 @@
 #include "../../include/xsd.h"
 
 #include "xsd_err.h"
+#include "xsd_mem.h"
 #define rfail xsd::failf      // the thread-local message of xsd_last_error()
 
 namespace {
@@ -479,10 +480,10 @@ struct SwBase {
     SwBase& operator=(const SwBase&) = delete;
     ~SwBase()
     {
-        if (wt) hipFree(wt);
-        if (wt3) hipFree(wt3);
-        if (mean) hipFree(mean);
-        if (ws_buf) hipFree(ws_buf);
+        if (wt) xsd::dev_free(wt);
+        if (wt3) xsd::dev_free(wt3);
+        if (mean) xsd::dev_free(mean);
+        if (ws_buf) xsd::dev_free(ws_buf);
     }
 };
 
@@ -531,8 +532,8 @@ int check_layers(const Cfg& c, const char* net)
 // the packed copy of the weights and the per-channel mean of the input; on failure the caller deletes the engine
 int alloc_weights(SwBase* r, const char* net, const std::vector<float>& mean)
 {
-    if (hipMalloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
-        hipMalloc((void**)&r->mean, sizeof(float) * mean.size()) != hipSuccess ||
+    if (xsd::dev_alloc((void**)&r->wt, sizeof(float) * std::max(1ll, r->wt_floats)) != hipSuccess ||
+        xsd::dev_alloc((void**)&r->mean, sizeof(float) * mean.size()) != hipSuccess ||
         hipMemcpy(r->mean, mean.data(), sizeof(float) * mean.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {      // (stream 0's upload is on the device before a forward on a non-blocking stream reads it)
         (void)hipGetLastError();
@@ -568,11 +569,11 @@ int grow_ws(SwBase* r, const char* net, long long floats, int B, int H, int W)
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + r->ws_bytes)
         return rfail(XSD_ERR_NOMEM, "%s: a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held "
                      "by this engine of %.1f GiB); use a smaller batch per call", net, need * gb, B, H, W, free_b * gb, r->ws_bytes * gb, total_b * gb);
-    if (r->ws_buf) { hipDeviceSynchronize(); hipFree(r->ws_buf); r->ws_buf = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
-    hipError_t err = hipMalloc((void**)&r->ws_buf, need);
+    if (r->ws_buf) { hipDeviceSynchronize(); xsd::dev_free(r->ws_buf); r->ws_buf = nullptr; r->ws_bytes = 0; r->B = r->H = r->W = 0; }
+    hipError_t err = xsd::dev_alloc((void**)&r->ws_buf, need);
     if (err != hipSuccess) {
         (void)hipGetLastError();
-        return rfail(XSD_ERR_NOMEM, "%s: workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s", net, need * gb, B, H, W, hipGetErrorString(err));
+        return rfail(XSD_ERR_NOMEM, "%s: workspace allocation (%.1f GiB for %d x %d x %d tiles) failed: %s", net, need * gb, B, H, W, hipGetErrorString(err));
     }
     r->ws_bytes = need;
     return XSD_OK;

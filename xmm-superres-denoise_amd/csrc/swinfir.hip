@@ -33,7 +33,7 @@ struct xsd_swinfir : SwBase {
     float2* tw = nullptr;             // roots of unity for H, then for W (device)
     int twH = 0, twW = 0;
 
-    ~xsd_swinfir() { if (tw) hipFree(tw); }
+    ~xsd_swinfir() { if (tw) xsd::dev_free(tw); }
 };
 
 namespace {
@@ -120,8 +120,12 @@ int set_twiddles(xsd_swinfir* r, int H, int W)
     if (r->twH == H && r->twW == W) return XSD_OK;
     std::vector<float2> t((size_t)H + W);
     fft_twiddles(H, W, t.data());                         // sw_fft.h
-    if (r->tw) { hipDeviceSynchronize(); hipFree(r->tw); r->tw = nullptr; r->twH = r->twW = 0; }
-    if (hipMalloc((void**)&r->tw, sizeof(float2) * t.size()) != hipSuccess) {
+    // The one place that pairs the planned shape with the table: a plan (r->B / H / W) is valid only for the table it was made with, so
+    // giving the table up clears it, for the forward and for xsd_swinfir_test_fft alike.  A forward at the shape held so far must not
+    // skip its plan and read a table that is gone (a smaller shape fits the held workspace, so grow_ws leaves the plan alone, and a
+    // refused allocation below would return with it set).
+    if (r->tw) { hipDeviceSynchronize(); xsd::dev_free(r->tw); r->tw = nullptr; r->twH = r->twW = 0; r->B = r->H = r->W = 0; }
+    if (xsd::dev_alloc((void**)&r->tw, sizeof(float2) * t.size()) != hipSuccess) {
         (void)hipGetLastError();
         return rfail(XSD_ERR_NOMEM, "SwinFIR: twiddle table allocation failed");
     }
@@ -151,7 +155,6 @@ int xsd_swinfir_fft_supported(int n)
 int xsd_swinfir_create(const xsd_swinfir_config* cfg, xsd_swinfir** out)
 {
     if (!cfg || !out) return rfail(XSD_ERR_ARG, "null argument");
-    *out = nullptr;
     const auto& c = *cfg;
     if (c.ape) return rfail(XSD_ERR_ARG, "SwinFIR: ape=True (absolute position embedding) is not supported by the MI355X engine");
     if (c.upsampler != 0)
@@ -297,8 +300,7 @@ int xsd_swinfir_test_fft(xsd_swinfir* r, float* dev_x, float* dev_spec, int B, i
     if (r->twH != H || r->twW != W) {
         hipStreamSynchronize(s);
         int rc = set_twiddles(r, H, W);
-        if (rc) return rc;
-        r->B = r->H = r->W = 0;          // the workspace plan no longer matches the twiddles: re-plan at the next forward
+        if (rc) return rc;              // (set_twiddles cleared the planned shape with the old table: the next forward plans again)
     }
     const FftShape fs{B, H, W, C2, r->tw};
     hipError_t e = inverse ? fft(fs, s, F_COLS_INV, dev_spec, dev_spec) : fft(fs, s, F_R2C_ROWS, dev_x, dev_spec);

@@ -233,7 +233,6 @@ extern "C" {
 int xsd_swinir_create(const xsd_swinir_config* cfg, xsd_swinir** out)
 {
     if (!cfg || !out) return rfail(XSD_ERR_ARG, "null argument");
-    *out = nullptr;
     const auto& c = *cfg;
     if (c.ape) return rfail(XSD_ERR_ARG, "SwinIR: ape=True (absolute position embedding) is not supported by the MI355X engine");
     if (c.upsampler < 0 || c.upsampler > 3) return rfail(XSD_ERR_ARG, "SwinIR: unknown upsampler %d", c.upsampler);
@@ -391,18 +390,18 @@ int xsd_swinir_test_pad(const float* dev_x, float* dev_y, int B, int C, int H, i
     hipStream_t s = (hipStream_t)stream;
     float* dmean = nullptr;
     if (mean) {
-        if (hipMalloc((void**)&dmean, sizeof(float) * C) != hipSuccess) {
+        if (xsd::dev_alloc((void**)&dmean, sizeof(float) * C) != hipSuccess) {
             (void)hipGetLastError();
             return rfail(XSD_ERR_NOMEM, "SwinIR pad test: allocation failed");
         }
         if (hipMemcpy(dmean, mean, sizeof(float) * C, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // on the device before the kernel on `s` reads it
-            hipFree(dmean);
+            xsd::dev_free(dmean);
             return rfail(XSD_ERR_HIP, "SwinIR pad test: upload of the mean failed");
         }
     }
     hipError_t e = pad(s, dev_x, dev_y, B, C, H, W, H + ph, W + pw, dmean, img_range);
     hipStreamSynchronize(s);
-    if (dmean) hipFree(dmean);
+    if (dmean) xsd::dev_free(dmean);
     if (e) return rfail(XSD_ERR_HIP, "SwinIR pad test: %s", hipGetErrorString(e));
     return XSD_OK;
 }

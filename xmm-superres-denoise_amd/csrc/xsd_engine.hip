@@ -755,11 +755,11 @@ static int ensure_plan(xsd_engine* e, int B, int H, int W, bool train)
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + e->ws_bytes)
             return fail(XSD_ERR_NOMEM, "a workspace of %.1f GiB for %d x %d x %d tiles does not fit this device (%.1f GiB free + %.1f GiB held by this engine of %.1f GiB)%s",
                         need * gb, B, H, W, free_b * gb, e->ws_bytes * gb, total_b * gb, hint);
-        if (e->ws) { hipDeviceSynchronize(); hipFree(e->ws); e->ws = nullptr; e->ws_bytes = 0; }
-        hipError_t err = hipMalloc((void**)&e->ws, need);
+        if (e->ws) { hipDeviceSynchronize(); xsd::dev_free(e->ws); e->ws = nullptr; e->ws_bytes = 0; }
+        hipError_t err = xsd::dev_alloc((void**)&e->ws, need);
         if (err != hipSuccess) {
             (void)hipGetLastError();      // the failed allocation must not surface again as the next launch's error
-            return fail(XSD_ERR_NOMEM, "workspace hipMalloc(%.1f GiB for %d x %d x %d tiles) failed: %s%s", need * gb, B, H, W, hipGetErrorString(err), hint);
+            return fail(XSD_ERR_NOMEM, "workspace allocation (%.1f GiB for %d x %d x %d tiles) failed: %s%s", need * gb, B, H, W, hipGetErrorString(err), hint);
         }
         e->ws_bytes = need;
     }
@@ -767,19 +767,19 @@ static int ensure_plan(xsd_engine* e, int B, int H, int W, bool train)
         const int cap = ((e->amax_used + xsd_engine::AMAX_TAIL + 4095) / 4096) * 4096;
         hipDeviceSynchronize();
         float* grown = nullptr;
-        hipError_t err = hipMalloc((void**)&grown, sizeof(float) * (size_t)cap);
+        hipError_t err = xsd::dev_alloc((void**)&grown, sizeof(float) * (size_t)cap);
         if (err == hipSuccess) err = hipMemset(grown, 0, sizeof(float) * (size_t)cap);
-        if (err != hipSuccess) { if (grown) hipFree(grown); return fail(XSD_ERR_NOMEM, "max-|x| slot array hipMalloc(%d floats) failed: %s", cap, hipGetErrorString(err)); }
+        if (err != hipSuccess) { if (grown) xsd::dev_free(grown); return fail(XSD_ERR_NOMEM, "max-|x| slot array allocation (%d floats) failed: %s", cap, hipGetErrorString(err)); }
         if (e->amax) {      // slots 0 / 1 hold the packed panels' maxima (written by the last xsd_pack_weights): they move along
             err = hipMemcpy(grown, e->amax, 2 * sizeof(float), hipMemcpyDeviceToDevice);
-            if (err != hipSuccess) { hipFree(grown); return fail(XSD_ERR_HIP, "max-|x| slot copy failed: %s", hipGetErrorString(err)); }
-            hipFree(e->amax);
+            if (err != hipSuccess) { xsd::dev_free(grown); return fail(XSD_ERR_HIP, "max-|x| slot copy failed: %s", hipGetErrorString(err)); }
+            xsd::dev_free(e->amax);
         }
         // hipMemset / hipMemcpy above run on stream 0, the launches that read the slots on the caller's stream, which may be non-blocking
         // (no implicit order with stream 0); neither call is documented to have completed on the device when it returns (a memset of
         // device memory may be asynchronous to the host; hipFree's implicit device synchronize runs only when there was an old array)
         err = hipDeviceSynchronize();
-        if (err != hipSuccess) { hipFree(grown); e->amax = nullptr; e->amax_cap = 0; return fail(XSD_ERR_HIP, "max-|x| slot array: %s", hipGetErrorString(err)); }
+        if (err != hipSuccess) { xsd::dev_free(grown); e->amax = nullptr; e->amax_cap = 0; return fail(XSD_ERR_HIP, "max-|x| slot array: %s", hipGetErrorString(err)); }
         e->amax = grown; e->amax_cap = cap;
     }
     e->amax_used = 2;
@@ -879,7 +879,7 @@ int xsd_create(const xsd_config* cfg, xsd_engine** out)
         e->generic = GenericNet::create(*cfg);
         if (!e->generic) { delete e; return fail(XSD_ERR_NOMEM, "generic-width engine: device allocation failed"); }
         e->nparams = e->generic->nparams;
-        if (hipMalloc((void**)&e->loss_partial, sizeof(double) * 1024) != hipSuccess) { xsd_destroy(e); return fail(XSD_ERR_NOMEM, "device allocation failed"); }
+        if (xsd::dev_alloc((void**)&e->loss_partial, sizeof(double) * 1024) != hipSuccess) { xsd_destroy(e); return fail(XSD_ERR_NOMEM, "device allocation failed"); }
         *out = e;
         return XSD_OK;
     }
@@ -946,29 +946,29 @@ int xsd_create(const xsd_config* cfg, xsd_engine** out)
     for (auto& c : e->up) add(c);
     if (cfg->kind == XSD_KIND_SR) add(e->hr);
     e->ndesc = (int)descs.size();
-#define CK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int rc = fail(XSD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); xsd_destroy(e); return rc; } } while (0)
-    CK(hipMalloc((void**)&e->pk_fwd, sizeof(float) * pk));
-    CK(hipMalloc((void**)&e->pk_bwd, sizeof(float) * pk));
-    CK(hipMalloc((void**)&e->pk_fwd_s, sizeof(float) * pk));
-    CK(hipMalloc((void**)&e->pk_bwd_s, sizeof(float) * pk));
+#define CK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int rc = fail(_e == hipErrorOutOfMemory ? XSD_ERR_NOMEM : XSD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); xsd_destroy(e); return rc; } } while (0)
+    CK(xsd::dev_alloc((void**)&e->pk_fwd, sizeof(float) * pk));
+    CK(xsd::dev_alloc((void**)&e->pk_bwd, sizeof(float) * pk));
+    CK(xsd::dev_alloc((void**)&e->pk_fwd_s, sizeof(float) * pk));
+    CK(xsd::dev_alloc((void**)&e->pk_bwd_s, sizeof(float) * pk));
     if (e->nf_pad) {
-        CK(hipMalloc((void**)&e->params_pad, sizeof(float) * e->nparams_pad));
-        CK(hipMalloc((void**)&e->grads_pad, sizeof(float) * e->nparams_pad));
-        CK(hipMalloc((void**)&e->pad_descs, sizeof(PadDesc) * pads.size()));
+        CK(xsd::dev_alloc((void**)&e->params_pad, sizeof(float) * e->nparams_pad));
+        CK(xsd::dev_alloc((void**)&e->grads_pad, sizeof(float) * e->nparams_pad));
+        CK(xsd::dev_alloc((void**)&e->pad_descs, sizeof(PadDesc) * pads.size()));
         CK(hipMemcpy(e->pad_descs, pads.data(), sizeof(PadDesc) * pads.size(), hipMemcpyHostToDevice));
     }
-    CK(hipMalloc((void**)&e->amax, sizeof(float) * e->amax_cap));
+    CK(xsd::dev_alloc((void**)&e->amax, sizeof(float) * e->amax_cap));
     CK(hipMemset(e->amax, 0, sizeof(float) * e->amax_cap));
-    CK(hipMalloc((void**)&e->zero_page, 512));   // [0,256): zeros (padding source); [256,512): trash (stores of lanes outside the image)
+    CK(xsd::dev_alloc((void**)&e->zero_page, 512));   // [0,256): zeros (padding source); [256,512): trash (stores of lanes outside the image)
     CK(hipMemset(e->zero_page, 0, 512));
-    CK(hipMalloc((void**)&e->pk_edge, sizeof(float) * 2 * 288 * e->planes * (cfg->in_channels + cfg->out_channels)));   // [first_fwd | first_bwd][in channel][plane][288], [last_fwd | last_bwd][out channel][plane][288]
-    CK(hipMalloc((void**)&e->pk_sbias, sizeof(float) * (sb ? sb : 1)));
-    CK(hipMalloc((void**)&e->descs_dev, sizeof(PackDesc) * descs.size()));
+    CK(xsd::dev_alloc((void**)&e->pk_edge, sizeof(float) * 2 * 288 * e->planes * (cfg->in_channels + cfg->out_channels)));   // [first_fwd | first_bwd][in channel][plane][288], [last_fwd | last_bwd][out channel][plane][288]
+    CK(xsd::dev_alloc((void**)&e->pk_sbias, sizeof(float) * (sb ? sb : 1)));
+    CK(xsd::dev_alloc((void**)&e->descs_dev, sizeof(PackDesc) * descs.size()));
     CK(hipMemcpy(e->descs_dev, descs.data(), sizeof(PackDesc) * descs.size(), hipMemcpyHostToDevice));
-    CK(hipMalloc((void**)&e->wg_partial, sizeof(float) * (size_t)e->nparts * 5 * PANEL_FLOATS));
-    CK(hipMalloc((void**)&e->wg_bias_partial, sizeof(float) * (size_t)e->nparts * 4 * 32));
-    CK(hipMalloc((void**)&e->edge_partial, sizeof(float) * EDGE_WGRAD_BLOCKS * 321));
-    CK(hipMalloc((void**)&e->loss_partial, sizeof(double) * 1024));
+    CK(xsd::dev_alloc((void**)&e->wg_partial, sizeof(float) * (size_t)e->nparts * 5 * PANEL_FLOATS));
+    CK(xsd::dev_alloc((void**)&e->wg_bias_partial, sizeof(float) * (size_t)e->nparts * 4 * 32));
+    CK(xsd::dev_alloc((void**)&e->edge_partial, sizeof(float) * EDGE_WGRAD_BLOCKS * 321));
+    CK(xsd::dev_alloc((void**)&e->loss_partial, sizeof(double) * 1024));
     // the hipMemset / hipMemcpy above went to stream 0; the first pack and forward may come on a non-blocking stream, which stream 0 does
     // not order: what they read (zeroed slots, the zero page, the descriptors) is on the device before create returns
     CK(hipDeviceSynchronize());
@@ -983,9 +983,10 @@ void xsd_destroy(xsd_engine* e)
     hipDeviceSynchronize();
     delete e->generic;
     for (auto ev : e->ev_pool) hipEventDestroy(ev);
-    hipFree(e->pk_fwd); hipFree(e->pk_bwd); hipFree(e->pk_fwd_s); hipFree(e->pk_bwd_s); hipFree(e->zero_page); hipFree(e->amax); hipFree(e->pk_edge); hipFree(e->pk_sbias); hipFree(e->descs_dev);
-    hipFree(e->wg_partial); hipFree(e->wg_bias_partial); hipFree(e->edge_partial); hipFree(e->loss_partial);
-    hipFree(e->ws); hipFree(e->params_pad); hipFree(e->grads_pad); hipFree(e->pad_descs);
+    xsd::dev_free(e->pk_fwd); xsd::dev_free(e->pk_bwd); xsd::dev_free(e->pk_fwd_s); xsd::dev_free(e->pk_bwd_s); xsd::dev_free(e->zero_page); xsd::dev_free(e->amax); xsd::dev_free(e->pk_edge); xsd::dev_free(e->pk_sbias); xsd::dev_free(e->descs_dev);
+    xsd::dev_free(e->wg_partial); xsd::dev_free(e->wg_bias_partial); xsd::dev_free(e->edge_partial); xsd::dev_free(e->loss_partial);
+    xsd::dev_free(e->ws); xsd::dev_free(e->params_pad); xsd::dev_free(e->grads_pad); xsd::dev_free(e->pad_descs);
+    xsd::dev_free(e->dbg);       // held while xsd_debug_stamps is on
     delete e;
 }
 
@@ -1157,7 +1158,7 @@ int xsd_loss_create(const xsd_loss_config* cfg, xsd_loss_fn** out)
 void xsd_loss_destroy(xsd_loss_fn* f)
 {
     if (!f) return;
-    hipFree(f->ws);
+    xsd::dev_free(f->ws);
     delete f;
 }
 
@@ -1178,9 +1179,9 @@ int xsd_loss_eval(xsd_loss_fn* f, const float* dev_y, const float* dev_target, f
     const size_t need = loss_workspace_bytes(B, H, W);
     if (need > f->ws_bytes) {
         HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-        if (f->ws) HIPCHK(hipFree(f->ws));
+        if (f->ws) HIPCHK(xsd::dev_free(f->ws));
         f->ws = nullptr; f->ws_bytes = 0;
-        if (hipMalloc(&f->ws, need) != hipSuccess) return fail(XSD_ERR_NOMEM, "loss workspace allocation failed");
+        if (xsd::dev_alloc(&f->ws, need) != hipSuccess) return fail(XSD_ERR_NOMEM, "loss workspace allocation failed");
         f->ws_bytes = need;
     }
     HIPCHK(launch_loss(f->w, dev_y, dev_target, dev_dy_or_null, dev_out8, B, f->channels, H, W, f->ws, (hipStream_t)stream));
@@ -1300,9 +1301,10 @@ int xsd_debug_stamps(xsd_engine* e, int enable, unsigned long long* out16)
     HIPCHK(hipDeviceSynchronize());
     if (out16 && e->dbg) HIPCHK(hipMemcpy(out16, e->dbg, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (enable) {
-        if (!e->dbg) HIPCHK(hipMalloc((void**)&e->dbg, 32 * sizeof(unsigned long long)));
+        if (!e->dbg && xsd::dev_alloc((void**)&e->dbg, 32 * sizeof(unsigned long long)) != hipSuccess)
+            return fail(XSD_ERR_NOMEM, "xsd_debug_stamps: allocation of the stamp buffer failed");
         HIPCHK(hipMemset(e->dbg, 0, 32 * sizeof(unsigned long long)));
-    } else if (e->dbg) { hipFree(e->dbg); e->dbg = nullptr; }
+    } else if (e->dbg) { xsd::dev_free(e->dbg); e->dbg = nullptr; }
     return XSD_OK;
 }
 

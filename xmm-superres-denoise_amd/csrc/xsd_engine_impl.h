@@ -13,6 +13,7 @@
 #include "../../include/xsd.h"
 #include "xsd_aux.h"
 #include "xsd_err.h"
+#include "xsd_mem.h"
 #include "generic_net.h"
 
 using namespace xsd;

@@ -29,11 +29,11 @@ struct DevMem {
     std::vector<void*> ptrs;
     template <class T> hipError_t alloc(T** p, size_t n)
     {
-        const hipError_t err = hipMalloc((void**)p, sizeof(T) * n);
+        const hipError_t err = xsd::dev_alloc((void**)p, sizeof(T) * n);
         if (err == hipSuccess) ptrs.push_back(*p);
         return err;
     }
-    ~DevMem() { for (void* p : ptrs) hipFree(p); }
+    ~DevMem() { for (void* p : ptrs) xsd::dev_free(p); }
 };
 } // namespace
 
@@ -503,5 +503,17 @@ int xsd_test_add_channels(float* dev_dst, const float* dev_src, int C, int64_t H
     hipStream_t s = (hipStream_t)stream;
     return finish(launch_add_channels(dev_dst, dev_src, C, HW, B, s), s, "add channels");
 }
+
+// ---- the device-memory ledger (xsd_mem.h) ------------------------------------------------------------------------
+int xsd_test_mem_stats(int64_t* out, int n)
+{
+    if (!out || n < 1 || n > 6) return fail(XSD_ERR_ARG, "xsd_test_mem_stats: null out or n outside 1..6");
+    int64_t all[6];
+    xsd::mem_stats(all);
+    memcpy(out, all, sizeof(int64_t) * n);
+    return XSD_OK;
+}
+
+int64_t xsd_test_mem_refuse(int64_t nth) { return xsd::mem_refuse(nth); }
 
 } // extern "C"
