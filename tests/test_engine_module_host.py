@@ -18,7 +18,7 @@ import make_engine_module_refusals as mr
 G = os.path.join(os.path.dirname(__file__), "golden")
 with open(os.path.join(G, "engine_module_refusals.json")) as f:
     TABLE = json.load(f)
-STATE = ("_engine", "_engine_dev", "_flat", "_plist", "_packed_key", "_math")
+STATE = ("_engine", "_engine_dev", "_flat", "_plist", "_math")
 CLASSES = list(mr.OK)
 
 
@@ -59,7 +59,7 @@ def test_state_after_construction_and_across_copies(cls):
     assert all(getattr(m, a) is None for a in STATE), {a: getattr(m, a) for a in STATE}
     mode = "fp32" if cls == "Restormer" else "bf16x6"
     assert m.set_math(mode) is m and m.get_math() == mode and m._math == mode
-    m._engine, m._engine_dev, m._flat, m._plist, m._packed_key = object(), "cuda:0", torch.zeros(1), [], (1, 2)     # as after a forward
+    m._engine, m._engine_dev, m._flat, m._plist = object(), "cuda:0", torch.zeros(1), []     # as after a forward
     keys = list(m.state_dict())
     for c in (copy.deepcopy(m), pickle.loads(pickle.dumps(m))):
         assert c._math == mode and c.get_math() == mode
@@ -103,9 +103,10 @@ def test_the_plumbing_exists_once():
     for cls in CLASSES:
         c = getattr(M, cls)
         assert issubclass(c, FlatParams)
-        for name in ("_get_engine", "_pack_if_changed", "__getstate__", "set_math", "get_math", "_check_input", "flatten_parameters",
-                     "_param_version"):
+        for name in ("_get_engine", "__getstate__", "set_math", "get_math", "_check_input", "flatten_parameters", "_param_version"):
             assert getattr(c, name) is getattr(FlatParams, name), (cls, name)
+        for name in ("_pack_if_changed", "_packed_key"):      # no cached pack decision: every forward packs
+            assert not hasattr(c, name) and not hasattr(mr.build(cls, mr.OK[cls]), name), (cls, name)
         assert "_make_engine" in vars(c) or any("_make_engine" in vars(b) for b in c.__mro__[1:] if b is not FlatParams), cls
     forward_only = set()
     for info in pkgutil.walk_packages(xmm_superres_denoise.__path__, "xmm_superres_denoise."):

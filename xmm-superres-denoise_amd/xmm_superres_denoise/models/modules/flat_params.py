@@ -1,7 +1,8 @@
 """What the engine-backed modules share (GeneratorRRDB_DN / _SR, Restormer, SwinFIR, HAT, SwinIR): the flat parameter buffer the engines
-read (include/xsd.h: "flat params": every parameter a view into one contiguous fp32 buffer in state_dict order) with the version
-counter that says when it changed, the engine handle and its re-pack rule, the math mode, the copy / pickle rule, the input checks and
-the one forward-only autograd function.  A module provides _make_engine, its constructor checks and its forward's size rule."""
+read (include/xsd.h: "flat params": every parameter a view into one contiguous fp32 buffer in state_dict order), the engine handle, the
+pack rule (every forward packs: torch's version counters miss the writes made through `.data`), the version sum a
+recomputing backward compares, the math mode, the copy / pickle rule, the input checks and the one forward-only autograd function.  A
+module provides _make_engine, its constructor checks and its forward's size rule."""
 from __future__ import annotations
 
 import torch
@@ -10,14 +11,35 @@ from torch.autograd.function import once_differentiable
 from xmm_superres_denoise.engine import XsdError
 
 
+def tracks_version(t: torch.Tensor) -> bool:
+    """False for a tensor born under torch.inference_mode(), also after its .data was pointed elsewhere (is_inference() is then False)"""
+    try:
+        t._version
+    except RuntimeError:
+        return False
+    return True
+
+
+def inference_refusal(name: str, whose: str) -> RuntimeError:
+    """What a forward that a backward may follow answers when the parameters were created under torch.inference_mode().  Such
+    parameters stay without a version counter for good: pointing their .data at a normal tensor (flatten_parameters does) makes
+    is_inference() answer False and changes nothing else -- reading `_version` raises, and so does any autograd op that would save
+    them.  Forwards without a graph run on them."""
+    return RuntimeError(f"{name}: {whose} parameters are inference tensors (built or loaded under torch.inference_mode()), which autograd "
+                        "cannot train; forwards under torch.no_grad() / inference_mode() work, for training build the module outside "
+                        "inference mode")
+
+
 class _ForwardOnlyFn(torch.autograd.Function):
-    """The forward of a module without a backward on the engine: works in any grad mode; a backward that reaches it is refused by name."""
+    """The forward of a module without a backward on the engine: works in any grad mode; a backward that reaches it is refused by name.
+    It packs on every call, as the RRDB generators' forward does, and reads no version counter: parameters that are inference tensors
+    (a module built under torch.inference_mode()) have none."""
 
     @staticmethod
     def forward(ctx, module, x, *params):
         ctx.network = module.NETWORK
         eng = module._get_engine(x.device)
-        module._pack_if_changed()
+        eng.pack(module._flat)
         return eng.forward(x.contiguous())
 
     @staticmethod
@@ -40,7 +62,6 @@ class FlatParams:
         self._engine_dev = None
         self._flat = None
         self._plist = None
-        self._packed_key = None
         self._math = None       # None: the engine's default
 
     # ---- copies and pickles (copy.deepcopy for EMA / SWA copies, torch.save(module), spawn-style launchers) --------------------
@@ -48,7 +69,7 @@ class FlatParams:
         """The engine handle belongs to this process and this module: a copy or an unpickled module builds its own (and lays its own
         flat parameter buffer, and packs) at its first forward, exactly like a freshly constructed one.  The math mode is carried."""
         st = self.__dict__.copy()
-        st["_engine"] = st["_engine_dev"] = st["_flat"] = st["_plist"] = st["_packed_key"] = None
+        st["_engine"] = st["_engine_dev"] = st["_flat"] = st["_plist"] = None
         return st
 
     # ---- math mode -----------------------------------------------------------------------------------------------------------------
@@ -84,18 +105,9 @@ class FlatParams:
             with torch.cuda.device(flat.device):
                 self._engine = self._make_engine()
             self._engine_dev = flat.device
-            self._packed_key = None
             if getattr(self, "_math", None) is not None:
                 self._engine.set_math(self._math)
         return self._engine
-
-    def _pack_if_changed(self):
-        """Re-pack after any parameter update torch knows of (optimizer step, load_state_dict, in-place edits: the version counters
-        of the parameters and of the flat buffer) or a new flat buffer."""
-        key = (self._flat.data_ptr(), self._param_version())
-        if key != self._packed_key:
-            self._engine.pack(self._flat)
-            self._packed_key = key
 
     # ---- forward -------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -148,6 +160,13 @@ class FlatParams:
 
     def _param_version(self) -> int:
         """Changes with every in-place update torch knows of: the parameters keep their OWN version counters when their .data is
-        pointed into the flat buffer (an optimizer step or load_state_dict bumps the parameter's, an update of the flat buffer itself
-        -- the fused Adam of parallel.py goes through a raw pointer and is sequenced by its caller -- the buffer's)."""
-        return self._flat._version + sum(p._version for p in self._plist)
+        pointed into the flat buffer (an optimizer step, load_state_dict or an in-place op on the parameter bumps the parameter's, an
+        update of the flat buffer itself -- the fused Adam of parallel.py goes through a raw pointer and is sequenced by its caller --
+        the buffer's).  It does NOT change with a write through `.data` (`p.data.mul_()`, the EMA idiom, `w.data.normal_()`): torch
+        bumps no counter for those, so nothing that must see every write may rest on this sum -- the packed copies do not (every
+        forward packs).  Read only where a backward can follow: its one user is the recomputing backward's guard, which shares the
+        blind spot with torch's own saved-tensor check.  Inference-tensor parameters have no counter and are refused by name."""
+        try:
+            return self._flat._version + sum(p._version for p in self._plist)
+        except RuntimeError as e:       # torch's bare "Inference tensors do not track version counter"
+            raise inference_refusal(type(self).__name__, "the") from e

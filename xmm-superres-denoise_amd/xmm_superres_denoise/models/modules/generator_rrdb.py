@@ -83,7 +83,9 @@ class _EngineFn(torch.autograd.Function):
         ctx.module = module
         ctx.need_dx = x.requires_grad
         ctx.recompute = bool(need and module.memory_efficient)
-        ctx.flat_version = module._param_version()
+        # the counters only where a backward can follow: parameters built under torch.inference_mode() have none, and no_grad forwards
+        # of such a module work
+        ctx.flat_version = module._param_version() if need else None
         # torch's convs take an empty batch (empty output, zero gradients: the reference's modules do, e.g. for an empty shard);
         # the C ABI refuses B < 1, so there is nothing to launch and the answer is made here
         ctx.empty = x.dim() == 4 and x.shape[0] == 0 and x.shape[1] == eng.in_channels

@@ -27,6 +27,7 @@ from torch import nn
 from xmm_superres_denoise import ops
 from xmm_superres_denoise.engine import XsdError
 
+from .flat_params import inference_refusal, tracks_version
 from .swinir import SwinIR
 
 
@@ -99,6 +100,8 @@ class TrainableSwin(nn.Module):
         self.module._check_input(x, self.module.in_chans)
         if not x.is_cuda:
             raise XsdError("the MI355X engine needs CUDA(HIP) tensors; there is no CPU fallback")
+        if torch.is_grad_enabled() and not all(tracks_version(p) for p in self.module.parameters()):
+            raise inference_refusal(type(self).__name__, f"the wrapped {type(self.module).__name__}'s")
 
     def _features(self, x: torch.Tensor, window: int | None = None) -> torch.Tensor:
         """conv_first .. conv_after_body + conv_first's output on the scaled image x [B, C, H, W] -> [B, H, W, E] token-major.  `window`:
