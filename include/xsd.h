@@ -651,6 +651,44 @@ int64_t xsd_sw_op_attention_scratch(int B, int H, int W, int C, int heads, int w
 int xsd_sw_op_attention_backward(const float* dev_dout, const float* dev_qkv, const float* dev_table, float* dev_dqkv, float* dev_dtable, int B,
                                  int H, int W, int C, int heads, int ws, int shift, float scale, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ---- differentiable HAT ops (csrc/hat_ops.hip) ----------------------------------------------------------------
+ * The two operations a trainable HAT needs on top of the differentiable Swin ops above (xmm_superres_denoise/ops.py:
+ * overlap_attention, channel_attention; models/modules/hat_train.py), under the same rules: every entry is asynchronous on `stream`,
+ * allocates nothing (`scratch`: at least the bytes of the matching *_scratch query, which returns -1 with xsd_last_error for a refused
+ * shape), fp32 with sums in double, no float atomics, every reduction in a fixed order (bitwise reproducible), and every element of
+ * every output is written.  Refusals (null pointers, shapes out of range, a scratch too small) name the op and come before anything
+ * is enqueued.
+ *
+ * overlap_attention: the OCAB's attention, the kernel and the arguments of xsd_hat_test_ocab (the same bits; the same limits: 1 <= ws
+ * <= 16, ws <= ow <= 32, ow - ws even, at most 32 channels per head, H and W multiples of ws).  backward: dev_dout [B][H W][C] and the
+ * forward's dev_out -> dev_dqkv [B][H W][3 C] and dev_dtable [(ws + ow - 1)^2][heads].  The probabilities are recomputed from qkv.  dk
+ * and dv leave as one slab per window in scratch and are summed per token over the windows that hold it, in ascending window order;
+ * the table gradient is one partial per (window, head), summed in a fixed order; a negative index lands in the bin the forward reads;
+ * keys outside the image get no dk / dv and do count in the table gradient.  B H W C <= 2^37.
+ * Scratch bytes, each term rounded up to a multiple of 256, with nwin = B (H / ws) (W / ws):
+ *   4 nwin ow^2 2 C   +   4 nwin (ws + ow - 1)^2 heads. */
+int xsd_hat_op_ocab_forward(const float* dev_qkv, const float* dev_table, float* dev_out, int B, int H, int W, int C, int heads, int ws, int ow,
+                            float scale, void* stream);
+int64_t xsd_hat_op_ocab_scratch(int B, int H, int W, int C, int heads, int ws, int ow);
+int xsd_hat_op_ocab_backward(const float* dev_dout, const float* dev_qkv, const float* dev_table, const float* dev_out, float* dev_dqkv,
+                             float* dev_dtable, int B, int H, int W, int C, int heads, int ws, int ow, float scale, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+/* channel_attention: t [B][HW][C] token-major, dev_w1 [Cs][C], dev_b1 [Cs], dev_w2 [C][Cs], dev_b2 [C] the squeeze MLP's 1x1 convs as
+ * stored -> dev_gates [B][C] (or NULL: kept in scratch) = sigmoid(w2 relu(w1 mean_p(t[b]) + b1) + b2), bitwise the dev_y of xsd_hat_test_ca_combine, and
+ * dev_y [B][HW][C] = t * gates[b].  backward: dev_dy and t -> dev_dt [B][HW][C] = dy g + dmean / HW, dev_dw1, dev_db1, dev_dw2, dev_db2
+ * (per-image partials summed over the images in ascending order).  The mean, the hidden vector and the gate are recomputed from t in
+ * double: the forward's fp32 gates are not an input (their rounding would go straight into dt).
+ * B <= 65535, HW <= 2^28, C and Cs in [1, 4096], B HW C <= 2^38.
+ * Scratch bytes, each term rounded up to a multiple of 256, with chunks = ceil(HW / 256):
+ *   forward   8 B chunks C   +   4 B C
+ *   backward  8 B chunks 2 C   +   8 B (3 C + Cs)   +   8 B (2 Cs C + Cs + C). */
+int xsd_hat_op_ca_forward(const float* dev_t, const float* dev_w1, const float* dev_b1, const float* dev_w2, const float* dev_b2, float* dev_y,
+                          float* dev_gates, int B, int64_t HW, int C, int Cs, void* scratch, int64_t scratch_bytes, void* stream);
+int64_t xsd_hat_op_ca_scratch(int B, int64_t HW, int C, int Cs, int backward);
+int xsd_hat_op_ca_backward(const float* dev_dy, const float* dev_t, const float* dev_w1, const float* dev_b1, const float* dev_w2,
+                           const float* dev_b2, float* dev_dt, float* dev_dw1, float* dev_db1, float* dev_dw2, float* dev_db2,
+                           int B, int64_t HW, int C, int Cs, void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ---- measurement / test hooks ------------------------------------------------------------------------------- */
 /* Per-kernel-class HIP-event timing of the kernels launched by this engine (bench.py roofline block), with each launch's
  * ALGORITHMIC flop and bytes (SURVEY.md 8d counting rule: every operand once).  MFMA-bound classes: 0 = conv (forward +

@@ -6,3 +6,4 @@ from .modules.swinfir import SwinFIR  # noqa: F401
 from .modules.swinir import SwinIR  # noqa: F401
 from .modules.swinir_train import TrainableSwinIR  # noqa: F401
 from .modules.swinfir_train import TrainableSwinFIR  # noqa: F401
+from .modules.hat_train import TrainableHAT  # noqa: F401

@@ -16,6 +16,12 @@ needs it; recomputing it would cost the whole GEMM again).
 What is saved: linear / conv3x3: the input, the weight and, with an activation, the pre-activation.  layer_norm: the input and the
 weight (mean and variance are recomputed in double).  window_attention: qkv and the table (the probabilities are recomputed; no
 ws^2 x ws^2 matrix is kept).
+
+HAT's two operations on top of them (include/xsd.h, "differentiable HAT ops"; csrc/hat_ops.hip), under the same rules:
+`overlap_attention`, the overlapping cross-attention of the OCAB (the kernel of engine.hat_ocab_attention: the same bits; saves qkv,
+the table and its output, from which the backward takes delta = dout . out; no ws^2 x ow^2 matrix is kept), and `channel_attention`,
+the gate at the end of the CAB (the gates are bitwise those of engine.hat_ca_combine; saves its input and the four weights; the
+backward recomputes the mean, the hidden vector and the gate in double, so the fp32 gate's rounding does not reach dt).
 """
 from __future__ import annotations
 
@@ -26,7 +32,7 @@ from .engine import XsdError, _lib
 from .engine._lib import check
 from .engine.engine import SW_ACT, _require_cuda_f32, _stream_ptr
 
-__all__ = ["linear", "conv3x3", "layer_norm", "window_attention", "LRELU_SLOPE"]
+__all__ = ["linear", "conv3x3", "layer_norm", "window_attention", "overlap_attention", "channel_attention", "LRELU_SLOPE"]
 
 LRELU_SLOPE = 0.01           # nn.LeakyReLU's default, what engine.sw_gemm's "lrelu" runs
 
@@ -230,3 +236,93 @@ def window_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, hea
     if qkv.dim() != 3 or qkv.shape[1] != H * W or qkv.shape[2] % 3 or tuple(table.shape) != ((2 * ws - 1) ** 2, heads):
         raise XsdError(f"qkv {tuple(qkv.shape)} / table {tuple(table.shape)} do not fit {H} x {W}, {heads} heads, window {ws}")
     return _WindowAttentionFn.apply(qkv, table, int(H), int(W), int(heads), int(ws), int(shift), float(scale), torch.is_grad_enabled())
+
+
+class _OverlapAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, H, W, heads, ws, ow, scale, grad_mode):
+        L = _lib.load()
+        B, _, C3 = (int(v) for v in qkv.shape)
+        with torch.cuda.device(qkv.device):
+            out = torch.empty((B, H * W, C3 // 3), device=qkv.device, dtype=torch.float32)
+            check(L.xsd_hat_op_ocab_forward(qkv.data_ptr(), table.data_ptr(), out.data_ptr(), B, H, W, C3 // 3, heads, ws, ow, scale,
+                                            _stream_ptr(qkv.device)))
+        if _needs_grad(ctx, grad_mode):
+            ctx.save_for_backward(qkv, table, out)
+            ctx.cfg = (B, H, W, C3 // 3, heads, ws, ow, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        qkv, table, out = ctx.saved_tensors
+        B, H, W, C, heads, ws, ow, scale = ctx.cfg
+        L = _lib.load()
+        dout = dout.contiguous()
+        _require_cuda_f32(dout, "dout")
+        with torch.cuda.device(qkv.device):
+            dqkv, dtable = torch.empty_like(qkv), torch.empty_like(table)
+            s = _scratch(L.xsd_hat_op_ocab_scratch(B, H, W, C, heads, ws, ow), qkv.device)
+            check(L.xsd_hat_op_ocab_backward(dout.data_ptr(), qkv.data_ptr(), table.data_ptr(), out.data_ptr(), dqkv.data_ptr(), dtable.data_ptr(),
+                                             B, H, W, C, heads, ws, ow, scale, s.data_ptr(), s.numel(), _stream_ptr(qkv.device)))
+        return dqkv, dtable, None, None, None, None, None, None, None
+
+
+def overlap_attention(qkv: torch.Tensor, table: torch.Tensor, H: int, W: int, heads: int, ws: int, ow: int, scale: float) -> torch.Tensor:
+    """The overlapping cross-attention of HAT's OCAB between its qkv Linear and proj: qkv [B, H W, 3 C] token rows in image order, table
+    [(ws + ow - 1)^2, heads] -> [B, H W, C] in image order.  The ws x ws queries of a window attend to the ow x ow keys / values of the
+    overlapping window around it (stride ws, zero padding (ow - ws) / 2); a key outside the image is a zero vector that stays in the
+    softmax with score = bias; the bias index is the reference's, negative entries wrapping.  ws 1..16, ws <= ow <= 32, ow - ws even, at
+    most 32 channels per head.  Gradients: qkv and table."""
+    _require_cuda_f32(qkv, "qkv")
+    _require_cuda_f32(table, "table")
+    if qkv.dim() != 3 or qkv.shape[1] != H * W or qkv.shape[2] % 3 or tuple(table.shape) != ((ws + ow - 1) ** 2, heads):
+        raise XsdError(f"qkv {tuple(qkv.shape)} / table {tuple(table.shape)} do not fit {H} x {W}, {heads} heads, window {ws}, overlap window {ow}")
+    return _OverlapAttentionFn.apply(qkv, table, int(H), int(W), int(heads), int(ws), int(ow), float(scale), torch.is_grad_enabled())
+
+
+class _ChannelAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, w1, b1, w2, b2, grad_mode):
+        L = _lib.load()
+        B, HW, C = (int(v) for v in t.shape)
+        Cs = int(b1.numel())
+        with torch.cuda.device(t.device):
+            y = torch.empty_like(t)
+            s = _scratch(L.xsd_hat_op_ca_scratch(B, HW, C, Cs, 0), t.device)
+            check(L.xsd_hat_op_ca_forward(t.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), y.data_ptr(), None,
+                                          B, HW, C, Cs, s.data_ptr(), s.numel(), _stream_ptr(t.device)))
+        if _needs_grad(ctx, grad_mode):
+            ctx.save_for_backward(t, w1, b1, w2, b2)
+            ctx.cfg = (B, HW, C, Cs)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        t, w1, b1, w2, b2 = ctx.saved_tensors
+        B, HW, C, Cs = ctx.cfg
+        L = _lib.load()
+        dy = dy.contiguous()
+        _require_cuda_f32(dy, "dy")
+        with torch.cuda.device(t.device):
+            dt, dw1, db1, dw2, db2 = (torch.empty_like(v) for v in (t, w1, b1, w2, b2))
+            s = _scratch(L.xsd_hat_op_ca_scratch(B, HW, C, Cs, 1), t.device)
+            check(L.xsd_hat_op_ca_backward(dy.data_ptr(), t.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), dt.data_ptr(),
+                                           dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), B, HW, C, Cs,
+                                           s.data_ptr(), s.numel(), _stream_ptr(t.device)))
+        return tuple(g if need else None for g, need in zip((dt, dw1, db1, dw2, db2), ctx.needs_input_grad)) + (None,)
+
+
+def channel_attention(t: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """The channel attention at the end of HAT's CAB: t [B, HW, C] (or [B, H, W, C]) token-major -> t * g[b, c] with
+    g = sigmoid(w2 relu(w1 mean_p t + b1) + b2); w1 [Cs, C, 1, 1] and w2 [C, Cs, 1, 1] as the 1x1 Conv2ds store them (or [Cs, C] and
+    [C, Cs]), b1 [Cs], b2 [C].  The mean is a double sum over chunks of 256 pixels in a fixed order.  Gradients: all five."""
+    for n, v in (("t", t), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+        _require_cuda_f32(v, n)
+    C, Cs = int(t.shape[-1]), int(b1.numel())
+    if t.dim() not in (3, 4) or w1.numel() != Cs * C or w2.numel() != C * Cs or b2.numel() != C or w1.shape[0] != Cs or w2.shape[0] != C:
+        raise XsdError(f"t {tuple(t.shape)}, w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, w2 {tuple(w2.shape)}, b2 {tuple(b2.shape)} are not "
+                       f"[B, HW, C] and a squeeze MLP of {C} channels")
+    y = _ChannelAttentionFn.apply(t.reshape(t.shape[0], -1, C), w1, b1, w2, b2, torch.is_grad_enabled())
+    return y.view(t.shape)

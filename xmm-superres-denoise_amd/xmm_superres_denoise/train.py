@@ -242,9 +242,25 @@ def fit_swinfir(ctor_kwargs: dict, steps: int = 10, batch_size: int = 1, lr_res:
                         batch_size, lr_res, data, lr, betas, loss, clamp, seed, checkpoint, device, log_every)
 
 
+def fit_hat(ctor_kwargs: dict, steps: int = 10, batch_size: int = 1, lr_res: int = 64, data=None, lr: float = 2e-4,
+            betas=(0.9, 0.999), loss="l1", clamp: bool = False, seed: int = 0, checkpoint: str | None = None,
+            device: str | None = None, log_every: int = 1):
+    """Train a HAT on the MI355X engine: `HAT(**ctor_kwargs)` (the reference's constructor arguments; upsampler "pixelshuffle",
+    resi_connection "1conv" or "identity"), wrapped in a TrainableHAT (models/modules/hat_train.py: the forward composed of the
+    differentiable HIP ops of xmm_superres_denoise/ops.py, with overlap_attention and channel_attention for the OCAB and the CAB).
+    Everything else is fit_swinir's: the data, the loss, the clamp, Adam with its moments in two flat buffers, the checkpoint layout
+    (the reference's key names with the `model.` prefix: infer.load_model(path, "hat") loads a checkpoint of the models.toml
+    configuration, HAT(**ctor_kwargs) loads its `state_dict` minus the prefix; load_checkpoint(path, trainer, trainer) restores the
+    moments).  The default lr is the reference's for [hat] (models.toml: learning_rate = 0.0002).  lr_res (one side, or (H, W)) must lie
+    on the window grid.  `fit` is untouched and keeps refusing "hat" by name.  Returns (trainable net, trainer, losses)."""
+    from xmm_superres_denoise.models import HAT, TrainableHAT
+    return _fit_wrapped("fit_hat", HAT, TrainableHAT, lambda m, h, w: (h * m.upscale, w * m.upscale), ctor_kwargs, steps, batch_size,
+                        lr_res, data, lr, betas, loss, clamp, seed, checkpoint, device, log_every)
+
+
 def _fit_wrapped(what, module_cls, wrapper_cls, out_size, ctor_kwargs, steps, batch_size, lr_res, data, lr, betas, loss, clamp, seed,
                  checkpoint, device, log_every):
-    """the one body of fit_swinir and fit_swinfir: a forward-only module of models/, its trainable wrapper, SwinIRTrainer"""
+    """the one body of fit_swinir, fit_swinfir and fit_hat: a forward-only module of models/, its trainable wrapper, SwinIRTrainer"""
     if torch.cuda.device_count() < 1:
         raise RuntimeError("train.py needs an MI355X (no HIP device visible); there is no CPU fallback")
     if loss != "l1" and not hasattr(loss, "value_and_grad"):
